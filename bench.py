@@ -26,13 +26,28 @@ replicas: every rank proves its own instance; value = max-over-ranks time / (ste
 `python bench.py --gpus N` without WORLD_SIZE starts torchrun with N ranks as a child
 process (before any GPU call) and exits with its status.
 
-Also in the JSON line (prove workload, outside the timed region):
+A plain run sets up, warms up, times the steps and prints the JSON line: metric, value,
+unit, ms_per_step, the configuration, and what the timed region's own HIP events give
+(roofline without its peaks and PMC traffic, msm_in_prover).  Every other leg runs only
+with --full.
+
+--dump-outputs DIR: after the timed steps, what the last timed step returned to its
+caller, as .npy files under DIR (written by rank 0): proof_bytes.npy, the proof, one
+float32 per byte (prove and keccak workloads), or msm_point_u32.npy, the MSM's affine
+point as 16 32-bit words in float64 (msm workload).  Inputs, SRS and prover rng are
+seeded, so two runs with the same arguments write the same files.
+
+--full adds to the JSON line (prove workload, outside the timed region):
   roofline     : dominant kernel = msm_acc_kernel (bucket accumulation), average
                  launch time from HIP events on the library stream over the timed
                  region; algorithmic bytes = 96 B/point x points per launch; PMC
                  traffic from rocprofv3 --pmc child passes (MI355X guide recipe);
                  bound "valu" with the modmul rate against the measured and modelled peaks
+  box          : this GPU's Montgomery product rate and clocks, measured before the
+                 timed region, and value_normalised by it
   verified     : the timed proof accepted by the checker's verifier (oracle/py/verifier.py)
+  stages_ms_synced_proof, pcie_inclusive, rngcore, ntt, k_range : further proofs and
+                 transforms, each timed on its own
   msm_2p24     : the metric's MSM half, 2^24 resident points, Mscalar-mul/s
   cpu_baseline : the CPU restatement (oracle/, halo2 algorithms, all cores) proving the
                  same circuit, witness and SRS at the same k, measured directly
@@ -121,6 +136,14 @@ def progress(msg):
     """a progress line on stderr (the JSON line alone goes to stdout): long legs -- the CPU
     baselines run for minutes -- must not look like a hang to a watchdog"""
     print(f"[bench {time.perf_counter() - T_START:7.1f} s] {msg}", file=sys.stderr, flush=True)
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: each array of the last timed step's result as DIRECTORY/<name>.npy"""
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def box_smi():
@@ -636,7 +659,7 @@ def run_prove(args, h2g, torch, dist, world, rank, dev, traffic, traffic_note):
         for _ in range(args.steps):
             step()
 
-    box = box_block(h2g) if rank == 0 else None  # before the timed region
+    box = box_block(h2g) if rank == 0 and args.full else None  # before the timed region
     progress(f"prove workload: {args.warmup} warm-up proofs")
     session(warm)
     torch.cuda.synchronize()
@@ -675,6 +698,9 @@ def run_prove(args, h2g, torch, dist, world, rank, dev, traffic, traffic_note):
             per_rank.append({"rank": r, "proof_ms": round(v[0], 3), "in_collectives_ms": round(cms, 3),
                              "compute_ms": round(v[0] - cms, 3), "collectives_per_proof": coll})
     elapsed = max_over_ranks(elapsed, dist, world, dev)
+    if rank == 0 and args.dump_outputs:  # the last timed step's proof, a float per byte
+        dump_outputs(args.dump_outputs,
+                     {"proof_bytes": np.frombuffer(proofs[-1], dtype=np.uint8).astype(np.float32)})
     line = None
     extra = {}
     if spmd:  # every rank wrote the proof: the same bytes on all ranks
@@ -685,14 +711,15 @@ def run_prove(args, h2g, torch, dist, world, rank, dev, traffic, traffic_note):
         extra["ranks_equal"] = all(bool(torch.equal(a, allh[0])) for a in allh)
     if rank == 0:
         assert all(p == proofs[0] for p in proofs), "non-deterministic proof bytes"
-        # outside the timed region: the proof checked by the independent verifier
+        # --full, outside the timed region: the proof checked by the independent verifier
         # (oracle/py/verifier.py, the checker), and one proof with synchronised stage
         # boundaries for a per-stage GPU time breakdown
-        extra["verified"] = verify_proof(h2g, circ, pk, params, proofs[0])
+        if args.full:
+            extra["verified"] = verify_proof(h2g, circ, pk, params, proofs[0])
         stages = []
         pcie = None
         rngcore = None
-        if not one_proof:
+        if args.full and not one_proof:
             h2g.prover_stage_sync(True)
             step()
             h2g.prover_stage_sync(False)
@@ -768,24 +795,27 @@ def run_prove(args, h2g, torch, dist, world, rank, dev, traffic, traffic_note):
                                        + " slabs + partials), NTT/evaluate_h/SHPLONK on rank 0" if shard else
                                        f"{world} independent provers")},
             "roofline": roofline_from_phases(calls, phases, n_local, traffic, traffic_note, union=union,
-                                             peak_gps=box["modmul_f29_gps"]),
-            "box": box,
-            "value_normalised": round(elapsed / (args.steps * (1 if one_proof else world)) *
-                                      box["modmul_f29_gps"] / MODMUL_F29_REF_GPS, 4),
-            "value_normalised_basis": f"value x box.modmul_f29_gps / {MODMUL_F29_REF_GPS} G/s (F29 products, the "
-                                      "hot kernels' arithmetic)",
-            "value_normalised_fips": round(elapsed / (args.steps * (1 if one_proof else world)) *
-                                           box["modmul_ref_gps"] / MODMUL_REF_GPS, 4),
+                                             peak_gps=box["modmul_f29_gps"] if box else None),
             "msm_in_prover": {"launches_per_proof": calls // max(args.steps, 1), "avg_ms": round(msm_ms, 4),
                               "busy_ms_per_proof": round(union["msm"] / args.steps, 3),
                               "accumulate_busy_ms_per_proof": round(union["accumulate"] / args.steps, 3),
                               "points_per_launch": n_local,
                               "mscalar_mul_per_s": round(n_local / (msm_ms * 1e-3) / 1e6, 2) if msm_ms else None,
                               "phases_ms": {kk: round(v / max(calls, 1), 4) for kk, v in phases.items()}},
-            "verified": extra["verified"],
-            "stages_ms_synced_proof": {nm: round(ms, 3) for nm, ms in stages},
         }
-        if world == 1 and args.workload == "prove":
+        if args.full:
+            line.update({
+                "box": box,
+                "value_normalised": round(elapsed / (args.steps * (1 if one_proof else world)) *
+                                          box["modmul_f29_gps"] / MODMUL_F29_REF_GPS, 4),
+                "value_normalised_basis": f"value x box.modmul_f29_gps / {MODMUL_F29_REF_GPS} G/s (F29 products, "
+                                          "the hot kernels' arithmetic)",
+                "value_normalised_fips": round(elapsed / (args.steps * (1 if one_proof else world)) *
+                                               box["modmul_ref_gps"] / MODMUL_REF_GPS, 4),
+                "verified": extra["verified"],
+                "stages_ms_synced_proof": {nm: round(ms, 3) for nm, ms in stages},
+            })
+        if args.full and world == 1 and args.workload == "prove":
             # the roofline's kernel figure from lone launches of the same MSM shape (no other
             # stream's kernels inside a launch); the in-proof launches' figures stay beside it
             rp = line["roofline"]
@@ -827,7 +857,7 @@ def run_prove(args, h2g, torch, dist, world, rank, dev, traffic, traffic_note):
                 line["transport"]["rccl_comm_rank0"] = rk
         if transport_note:
             line["transport_note"] = transport_note
-    if args.workload == "prove" and (world == 1 or dist.get_backend() == "nccl"):
+    if args.full and args.workload == "prove" and (world == 1 or dist.get_backend() == "nccl"):
         # every rank takes part when sharded (collectives inside)
         progress("MSM 2^24 leg")
         m = measure_msm(h2g, torch, dev, 24, steps=10, warmup=2, dist=dist, world=world, rank=rank)
@@ -838,13 +868,14 @@ def run_prove(args, h2g, torch, dist, world, rank, dev, traffic, traffic_note):
     if not worker:
         pk.close()
         del adv
-    want_cpu = line is not None and world == 1 and not args.no_cpu_baseline and args.workload == "prove"
+    want_cpu = (args.full and line is not None and world == 1 and not args.no_cpu_baseline
+                and args.workload == "prove")
     g = gl = None
     if want_cpu:
         g, gl = params.export()
     params.close()
     torch.cuda.empty_cache()
-    if line is not None and world == 1 and args.workload == "prove" and not args.no_krange:
+    if args.full and line is not None and world == 1 and args.workload == "prove" and not args.no_krange:
         progress("k-range proofs")
         line["k_range"] = k_range(h2g, torch, dev, args)
     if want_cpu:
@@ -1116,6 +1147,10 @@ def run_msm(args, h2g, torch, dist, world, rank, dev, traffic, traffic_note):
         result["total"] = combine_partials(result["parts"], h2g.g1_add_affine)
     if rank != 0:
         return None
+    if args.dump_outputs:  # the last timed step's point (the ranks' sum at N > 1), 32-bit words
+        point = result["total"] if world > 1 else result["p"]
+        dump_outputs(args.dump_outputs,
+                     {"msm_point_u32": np.ascontiguousarray(point, dtype=np.uint64).view(np.uint32).astype(np.float64)})
     h2g.descriptor_free(base)
     c = args.window_bits or fixed_c(n)
     return {
@@ -1174,6 +1209,11 @@ def main():
                     help="N > 1: seconds any wait on libh2g's RCCL communicators may take (setup, each "
                          "collective); past it they are aborted, the proof fails on that rank, and every "
                          "rank moves to the next transport of --spmd-transports")
+    ap.add_argument("--full", action="store_true",
+                    help="run every other leg too, outside the timed steps: box calibration, PMC passes, the "
+                         "verifier, stage / PCIe / RngCore proofs, lone MSM, NTT, MSM 2^24, k range, CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--sync-exchange", action="store_true",
                     help="spmd over the library's RCCL communicators: skip the overlapped column exchanges (the "
@@ -1205,8 +1245,8 @@ def main():
     if args.gpus != world_env:
         print(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world_env}", file=sys.stderr)
         return 2
-    traffic, traffic_note = (None, "skipped (--no-pmc)")
-    if not args.no_pmc and world_env == 1:
+    traffic, traffic_note = (None, "skipped (--no-pmc)" if args.full else "skipped (a --full leg)")
+    if args.full and not args.no_pmc and world_env == 1:
         traffic, traffic_note = pmc_traffic(args)
 
     import torch
@@ -1238,7 +1278,7 @@ def main():
     run = run_msm if args.workload == "msm" else run_prove
     line = run(args, h2g, torch, dist, world, rank, dev, traffic, traffic_note)
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1 and args.workload == "msm":
+        if args.full and not args.no_cpu_baseline and world == 1 and args.workload == "msm":
             cb = cpu_baseline_msm()
             line["cpu_baseline"] = cb
             line["gpu_vs_cpu"] = round(line["value"] / cb["value"], 1)

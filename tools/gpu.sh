@@ -20,17 +20,17 @@ case "$CMD" in
       -p no:cacheprovider "$@" > "$O/pytest.log" 2>&1
     rc=$?; tail -5 "$O/pytest.log"; exit $rc ;;
   bench)
-    timeout -k 10 900 python3 -u bench.py "$@" > "$O/bench.json" 2> "$O/bench.err"
+    timeout -k 10 900 python3 -u bench.py --full "$@" > "$O/bench.json" 2> "$O/bench.err"
     rc=$?; tail -c 3000 "$O/bench.json"; exit $rc ;;
   prof)
     cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/trace" -o prof -- \
-      python3 "$R/bench.py" --no-cpu-baseline --no-pmc --no-krange "$@" > "$O/bench_traced.json" 2> "$O/bench_traced.err"
+      python3 "$R/bench.py" --full --no-cpu-baseline --no-pmc --no-krange "$@" > "$O/bench_traced.json" 2> "$O/bench_traced.err"
     rc=$?; tail -c 1500 "$O/bench_traced.json"; exit $rc ;;
   pmc)
     cd /tmp
     for C in FETCH_SIZE WRITE_SIZE; do
       timeout -s KILL 300 rocprofv3 --pmc $C --output-format csv -d "$O/pmc_$C" -o pmc -- \
-        python3 "$R/bench.py" --no-cpu-baseline --no-pmc --no-krange "$@" > "$O/pmc_$C.log" 2>&1 || { echo "pmc $C failed"; exit 1; }
+        python3 "$R/bench.py" --full --no-cpu-baseline --no-pmc --no-krange "$@" > "$O/pmc_$C.log" 2>&1 || { echo "pmc $C failed"; exit 1; }
     done
     echo pmc ok ;;
   pmcbin)  # a standalone binary under one --pmc pass per counter (tools/microbench/pmc_calib)
