@@ -338,6 +338,56 @@ int h2g_rng_chacha20(const uint8_t seed[32], h2g_rng* out, uint64_t* handle);
 int h2g_rng_free(uint64_t handle);
 /* the challenges of the last proof (num_challenges x 4 u64), *count = num_challenges */
 int h2g_last_challenges(uint64_t* out, int max, int* count);
+/* ---- which constraints does a witness leave unsatisfied? ----------------------------
+ * MockProver::verify (halo2_frontend/src/dev.rs:742-1166) for a complete witness of ONE
+ * circuit, on the device, before any proof is made.  h2g_create_proof* accepts any advice;
+ * this call says which gate, lookup, shuffle or copy is wrong and at which row.
+ * Let u = n - (blinding_factors + 1).  The library works on its own copy of the advice
+ * (uploaded as h2g_create_proof uploads it) and fills rows [u, n) the way the prover will:
+ * zero for unblinded columns, Fr::random of a ChaCha20 stream seeded from `seed` for the
+ * others.  This is the one deliberate difference from MockProver, so that "no failures"
+ * means "the proof will verify": a gate that is live in a blinding row, or reads a blinded
+ * cell from a usable row, fails with overwhelming probability (kind 2, or kind 1 at the
+ * reading row).
+ *   gates    every gate polynomial at all n rows, rotations mod n, challenges from
+ *            `challenges` (MockProver's self.challenges)              dev.rs:849-925
+ *   lookups  the input tuple of every row < u must occur among the table tuples of rows < u
+ *                                                                     dev.rs:957-1052
+ *   shuffles the input and shuffle tuples of rows < u must be equal as multisets; one
+ *            record per failing shuffle, row = H2G_CHECK_NO_ROW       dev.rs:1054-1112
+ *   copies   the two cells of every listed copy must be equal          dev.rs:1114-1142
+ * Lookup and shuffle tuples are compared through their theta-compression with theta drawn
+ * from `seed`: PROBABILISTIC, a wrong m-expression argument over n rows passes with
+ * probability about m n / r (r the 254-bit field order).  Gates and copies are exact.
+ * Returns H2G_OK whether or not there are failures: *total is their exact number, out
+ * receives min(*total, cap) records sorted by (kind, index, row) -- when *total > cap, any cap
+ * of the failures.  out == NULL or cap == 0 only counts.  H2G_ERR_ARG: challenges missing
+ * on a key with challenges, a copy naming a column or row out of range, misaligned device
+ * advice, a missing advice or instance array; H2G_ERR_HANDLE: unknown key.  Synchronous;
+ * the key stays usable and later proofs have the bytes they would have had.  Shard and SPMD
+ * transports take no part. */
+enum {
+  H2G_CHECK_GATE = 1,          /* gate `index` is nonzero at usable row `row` */
+  H2G_CHECK_GATE_BLINDING = 2, /* gate `index` is nonzero at row >= n - (blinding_factors + 1) */
+  H2G_CHECK_LOOKUP = 3,        /* lookup `index`: input of usable row `row` not in the table */
+  H2G_CHECK_SHUFFLE = 4,       /* shuffle `index`: the multisets differ; row = H2G_CHECK_NO_ROW */
+  H2G_CHECK_COPY = 5           /* copies[index]: the two cells differ; row = its left row */
+};
+#define H2G_CHECK_NO_ROW 0xFFFFFFFFu
+typedef struct {
+  uint32_t kind, index, row, reserved;
+} h2g_check_failure;
+typedef struct {
+  const uint64_t* advice;     /* num_advice x n Fr, as h2g_create_proof */
+  int advice_on_device;       /* advice is a device pointer, 16-byte aligned */
+  const uint64_t* instance;   /* num_instance x n Fr, zero padded */
+  const uint64_t* challenges; /* num_challenges x 4 (Montgomery); required iff the key has challenges */
+  const uint8_t* seed;        /* 32 bytes; NULL = a fixed default */
+  const int32_t* copies;      /* h2g_circuit.copies layout; NULL / 0 skips the copy check */
+  uint32_t num_copies;
+} h2g_check_inputs;
+int h2g_check_witness(uint64_t pk, const h2g_check_inputs* in, h2g_check_failure* out, size_t cap, uint64_t* total);
+
 /* wall milliseconds of the stages of the last h2g_create_proof (names: h2g_prover_stage_name).
  * Stages end when their work is queued, unless h2g_prover_stage_sync(1) is set: then each
  * stage boundary synchronises the prover stream and the times are GPU completion times

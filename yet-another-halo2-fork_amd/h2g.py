@@ -104,6 +104,7 @@ _SIGS = {
     "h2g_create_proof_phased": ([U64, U64, VP, U64P, ctypes.POINTER(U32), ctypes.c_char_p, U32, ctypes.c_char_p,
                                  SZ, ctypes.POINTER(SZ)], I32),
     "h2g_create_proof_multi": ([U64, U64, VP, ctypes.c_char_p, SZ, ctypes.POINTER(SZ)], I32),
+    "h2g_check_witness": ([U64, VP, VP, SZ, ctypes.POINTER(U64)], I32),
     "h2g_last_challenges": ([U64P, I32, ctypes.POINTER(I32)], I32),
     "h2g_prover_stages": ([ctypes.POINTER(ctypes.c_double), I32, ctypes.POINTER(I32)], I32),
     "h2g_prover_stage_name": ([I32], ctypes.c_char_p),
@@ -601,6 +602,22 @@ class ProveInputs(ctypes.Structure):
                 ("rng_seed", ctypes.POINTER(ctypes.c_uint8)), ("vanishing_threads", U32)]
 
 
+class CheckFailure(ctypes.Structure):
+    """struct h2g_check_failure (include/h2g.h)"""
+    _fields_ = [("kind", U32), ("index", U32), ("row", U32), ("reserved", U32)]
+
+
+class CheckInputs(ctypes.Structure):
+    """struct h2g_check_inputs (include/h2g.h)"""
+    _fields_ = [("advice", VP), ("advice_on_device", I32), ("instance", VP), ("challenges", VP),
+                ("seed", VP), ("copies", VP), ("num_copies", U32)]
+
+
+# h2g_check_failure.kind, and the row of a failure that has none
+CHECK_GATE, CHECK_GATE_BLINDING, CHECK_LOOKUP, CHECK_SHUFFLE, CHECK_COPY = 1, 2, 3, 4, 5
+CHECK_NO_ROW = 0xFFFFFFFF
+
+
 def _ptr(a, t):
     return a.ctypes.data_as(t) if a is not None and a.size else None
 
@@ -746,6 +763,50 @@ class ProvingKey:
                                      buf, cap, ctypes.byref(ln)))
         del adv
         return buf.raw[: ln.value]
+
+    def check_witness(self, wit, challenges=None, seed=None, copies=True, cap=64, advice_dev_ptr=None):
+        """h2g_check_witness: MockProver::verify of a complete witness on the device ->
+        (total, [(kind, index, row), ...]) with min(total, cap) records sorted by (kind, index,
+        row); kinds CHECK_*, row CHECK_NO_ROW for a shuffle.  challenges: canonical ints, one
+        per challenge of the circuit; seed: 32 bytes (None: the library's default); copies:
+        True checks self.circ.copies, False none, an (m, 6) array that list; advice_dev_ptr: device pointer to num_advice x n Fr (wit
+        then supplies only the instance columns)."""
+        import h2g_circuit as hc
+
+        circ = self.circ
+        keep = []
+        inp = CheckInputs()
+        if advice_dev_ptr is not None:
+            inp.advice, inp.advice_on_device = advice_dev_ptr, 1
+        else:
+            adv = np.ascontiguousarray(wit.advice, dtype=np.uint64)
+            keep.append(adv)
+            inp.advice, inp.advice_on_device = (adv.ctypes.data if adv.size else None), 0
+        if circ.num_instance:
+            ins = np.ascontiguousarray(wit.instance, dtype=np.uint64)
+            keep.append(ins)
+            inp.instance = ins.ctypes.data
+        if challenges is not None and len(challenges):
+            ch = hc.ints_to_mont([int(c) for c in challenges])
+            keep.append(ch)
+            inp.challenges = ch.ctypes.data
+        if seed is not None:
+            sd = (ctypes.c_uint8 * 32)(*bytes(seed))
+            keep.append(sd)
+            inp.seed = ctypes.cast(sd, VP)
+        if isinstance(copies, bool):  # (an array instead: that copy list, in circ.copies' layout)
+            copies = circ.copies if copies else ()
+        if len(copies):
+            cp = np.ascontiguousarray(copies, dtype=np.int32).reshape(-1, 6)
+            keep.append(cp)
+            inp.copies, inp.num_copies = cp.ctypes.data, len(cp)
+        out = (CheckFailure * max(cap, 1))()
+        total = U64()
+        check(lib().h2g_check_witness(self.handle, ctypes.byref(inp), ctypes.cast(out, VP) if cap else None, cap,
+                                      ctypes.byref(total)))
+        del keep
+        got = min(total.value, cap)
+        return total.value, [(out[i].kind, out[i].index, out[i].row) for i in range(got)]
 
     def create_proof_phased(self, fill, wit, seed=bytes([7] * 32), vanishing_threads=8, multiopen="shplonk",
                             transcript="blake2b"):
