@@ -248,6 +248,13 @@ int h2g_pk_read(uint64_t params, const h2g_circuit* circuit, const uint8_t* buf,
                 uint64_t* pk);
 /* degree, blinding_factors, extended_k, #perm sets, #advice/#fixed/#instance queries */
 int h2g_pk_info(uint64_t pk, int32_t info[8]);
+/* Diagnostics (read only): the value width in bits that the next proof's sort will assume
+ * for every lookup, entry circuit * num_lookups + lookup, as the proofs made with this key
+ * so far measured it: <= 48 the value itself is the sort key, wider a 48-bit window below
+ * the top bit (with an order check), 0 the full 256-bit sort, 64 before the first proof.
+ * The list covers as many circuits as the largest proof so far proved at once (one after
+ * keygen).  Writes min(*count, max) entries; out may be NULL when max is 0. */
+int h2g_pk_lookup_sort_hints(uint64_t pk, int32_t* out, int max, int* count);
 /* the verifying key's commitments: VerifyingKey::fixed_commitments() (plonk.rs:228-231) and
  * the permutation VerifyingKey's commitments (plonk/permutation.rs:18-47), G1Affine (8 u64 each):
  * fixed[num_fixed], perm[num_perm_columns]; either may be NULL */

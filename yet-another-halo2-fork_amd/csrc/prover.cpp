@@ -4652,6 +4652,17 @@ int h2g_pk_info(uint64_t pk, int32_t info[8]) {
   return H2G_OK;
 }
 
+int h2g_pk_lookup_sort_hints(uint64_t pk, int32_t* out, int max, int* count) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  auto it = g_pks.find(pk);
+  if (it == g_pks.end()) return fail(H2G_ERR_HANDLE, "unknown proving key");
+  if (!count || max < 0 || (max > 0 && !out)) return fail(H2G_ERR_ARG, "pk_lookup_sort_hints: bad arguments");
+  const std::vector<int>& hb = it->second->lk_hb;
+  *count = (int)hb.size();
+  for (int i = 0; i < max && i < (int)hb.size(); i++) out[i] = (int32_t)hb[i];
+  return H2G_OK;
+}
+
 }  // extern "C"
 
 namespace {

@@ -97,6 +97,7 @@ _SIGS = {
     "h2g_pk_free": ([U64], I32),
     "h2g_pk_info": ([U64, ctypes.POINTER(ctypes.c_int32)], I32),
     "h2g_pk_vk_commitments": ([U64, U64P, U64P], I32),
+    "h2g_pk_lookup_sort_hints": ([U64, ctypes.POINTER(ctypes.c_int32), I32, ctypes.POINTER(I32)], I32),
     "h2g_pk_set_multiopen": ([U64, I32], I32),
     "h2g_pk_set_transcript": ([U64, I32], I32),
     "h2g_create_proof": ([U64, U64, VP, I32, U64P, ctypes.POINTER(U32), ctypes.c_char_p, U32, ctypes.c_char_p, SZ,
@@ -732,6 +733,15 @@ class ProvingKey:
         p = np.zeros((max(len(self.circ.perm_columns), 1), 8), dtype=np.uint64)
         check(lib().h2g_pk_vk_commitments(self.handle, p64(f), p64(p)))
         return f[: self.circ.num_fixed], p[: len(self.circ.perm_columns)]
+
+    def lookup_sort_hints(self):
+        """h2g_pk_lookup_sort_hints (diagnostics): per circuit x lookup, the value width in bits
+        the next proof's sort will assume (<= 48 value keys, wider a 48-bit window, 0 full sort)"""
+        cnt = ctypes.c_int()
+        check(lib().h2g_pk_lookup_sort_hints(self.handle, None, 0, ctypes.byref(cnt)))
+        out = (ctypes.c_int32 * max(cnt.value, 1))()
+        check(lib().h2g_pk_lookup_sort_hints(self.handle, out, cnt.value, ctypes.byref(cnt)))
+        return list(out)[: cnt.value]
 
     def write(self, fmt=RAW_BYTES):
         """ProvingKey::write (plonk.rs:311-321) -> bytes"""
