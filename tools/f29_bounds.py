@@ -224,7 +224,7 @@ def backend_class(C, add_ks, dbl_ks, thr):
     return max(out_add + out_dbl)
 
 
-def ntt_pass(stages, b0, kexpr, off, tw=MR):
+def ntt_pass(stages, b0, kexpr, off):
     """one NTT pass in F29 (csrc/ntt.hip ntt_pass29_kernel / ntt_last29_kernel): inputs <
     b0; stage s: sums a + b, differences a - b + K_s M (nsub29<S>) into a product with a
     twiddle < M, or kept (normalised) for the j = 0 butterflies; closing product with a
@@ -237,7 +237,7 @@ def ntt_pass(stages, b0, kexpr, off, tw=MR):
         # a product's operand: limbs 0..7 < 2^29 + 2^30, the twiddle normalised
         column_ok(N29, sub_limb(off))
     assert top(B) < 1 << 31, LG(B)         # top limb of a normalised value fits its 32 bits
-    return B * tw // R + MR + 1
+    return B * MR // R + MR + 1
 
 
 def check(consts=None, verbose=False):
@@ -288,11 +288,6 @@ def check(consts=None, verbose=False):
     out_sp = ys * MR // R + MR + 1
     assert out_sp < b0
     say(f"sparse first pass: outputs < {out_sp / MR:.3f} M")
-    tw_live = MR * MR // R + MR + 1  # a twiddle formed in the pass: lo x hi, both < M (H2G_NTT_TW_LIVE)
-    for st in (3, 4, 5, 6):
-        out = ntt_pass(st, b0, nk, no, tw_live)
-        assert out < b0 and out < 1 << 256, (st, out / MR)
-    say(f"passes with twiddles formed in the pass (< {tw_live / MR:.4f} M): outputs < {ntt_pass(6, b0, nk, no, tw_live) / MR:.3f} M")
     # evaluate_h29_kernel's unreduced sums / differences (eh_addn / eh_add3n / eh_subn): each
     # feeds one product; loads < 32 M, constants < M, reduced values < 1.001 M, Horner
     # accumulators reduced after every step
@@ -341,7 +336,7 @@ def check(consts=None, verbose=False):
     qv = top(tot) // (top(MR) + 1)
     assert MR + (qv + 2) * (1 << 232) < 2 * MR
     say(f"lincomb: pairs < {pair / MR:.4f} M, sum < {tot / MR:.2f} M, reduced below 2 M before the subtraction")
-    # H2G_HORNER29 (eval_level1, kate_phase1/3): acc <- REDC(acc x) + a with x < M and a
+    # the F29 Horner chains (eval_level1, kate_phase1/3): acc <- REDC(acc x) + a with x < M and a
     # storage integer a < 2^256; kate_phase3 (ACC) adds one more stored value before reducing
     h = 0
     for _ in range(200):

@@ -203,22 +203,13 @@ int msm_fixed_host_impl(Device* d, const void* sc, const MsmFixedBase& fb, size_
   return H2G_OK;
 }
 
-#ifndef H2G_MSM_HIPRIO
-#define H2G_MSM_HIPRIO 0
-#endif
 // the asynchronous MSMs' streams, result ring and events (h2g_init creates them, right
 // after the device stream: see there)
 int msm_ring_init(Device* d) {
   if (d->h_ring) return H2G_OK;
   HIPCHK(hipHostMalloc(&d->h_ring, MSM_RING * sizeof(G1xyzz), hipHostMallocDefault));
-  if (H2G_MSM_HIPRIO) {  // A/B: the MSM streams at the device's greatest stream priority
-    int least = 0, greatest = 0;
-    HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    for (int i = 0; i < MSM_STREAMS; i++)
-      HIPCHK(hipStreamCreateWithPriority(&d->mstream[i], hipStreamNonBlocking, greatest));
-  } else {
-    for (int i = 0; i < MSM_STREAMS; i++) HIPCHK(hipStreamCreateWithFlags(&d->mstream[i], hipStreamNonBlocking));
-  }
+  // (the MSM streams at the device's greatest stream priority: measured, rejected)
+  for (int i = 0; i < MSM_STREAMS; i++) HIPCHK(hipStreamCreateWithFlags(&d->mstream[i], hipStreamNonBlocking));
   for (int i = 0; i < MSM_RING; i++) HIPCHK(hipEventCreateWithFlags(&d->ring_ev[i], hipEventDisableTiming));
   return H2G_OK;
 }
@@ -468,15 +459,10 @@ extern "C" {
 int h2g_abi_version(void) { return 1; }
 const char* h2g_last_error(void) { return g_err.c_str(); }
 
-// A/B: k idle streams created ahead of the device stream shift every stream's hardware
-// queue by k.  C3 k = 22: 72.5-73.1 ms at 0, 72.8-73.7 at 1, 75.4-76.9 at 2, 76.2-77.1 at 3
-// (keccak-style within 0.5 ms; profiles/r06/xs/ab_queue_shift.log)
-#ifndef H2G_QUEUE_SHIFT
-#define H2G_QUEUE_SHIFT 0
-#endif
-#ifndef H2G_EAGER_STREAMS  // A/B builds: 0 = the MSM streams created by the first asynchronous MSM
-#define H2G_EAGER_STREAMS 1
-#endif
+// Measured, rejected: k idle streams created ahead of the device stream, which shift every
+// stream's hardware queue by k.  C3 k = 22: 72.5-73.1 ms at 0, 72.8-73.7 at 1, 75.4-76.9 at
+// 2, 76.2-77.1 at 3 (keccak-style within 0.5 ms; profiles/r06/xs/ab_queue_shift.log).  Also
+// rejected: the MSM streams created by the first asynchronous MSM instead of here.
 int h2g_init(const int* devices, int ndev) {
   std::lock_guard<std::recursive_mutex> lk(g_mu);
   if (!g_devs.empty()) return H2G_OK;
@@ -499,12 +485,8 @@ int h2g_init(const int* devices, int ndev) {
     // first single-GPU proof with lookups (prove_impl), so that multi-GPU runs leave the
     // fourth queue to the communicators' streams (an emulated C3 N = 8 replay lost 1 ms
     // with it taken: profiles/r06/emulation_final/).
-    for (int q = 0; q < H2G_QUEUE_SHIFT; q++) {  // A/B: idle streams ahead of the device stream
-      hipStream_t idle = nullptr;
-      HIPCHK(hipStreamCreateWithFlags(&idle, hipStreamNonBlocking));
-    }
     HIPCHK(hipStreamCreateWithFlags(&dev->stream, hipStreamNonBlocking));
-    if (H2G_EAGER_STREAMS) RCCHK(msm_ring_init(dev.get()));
+    RCCHK(msm_ring_init(dev.get()));
     HIPCHK(ntt_init_attributes());
     g_devs.push_back(std::move(dev));
   }

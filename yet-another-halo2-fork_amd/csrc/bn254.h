@@ -706,11 +706,11 @@ __device__ __forceinline__ G1Affine xyzz_to_affine_by(const G1xyzz& p) {
 }
 
 // ---------------------------------------------------------------- lazy [0, 2M) arithmetic (device)
-// For long chains of group additions that never leave the device (the MSM bucket
-// accumulation): values live in [0, 2M), so a Montgomery product skips its final
-// conditional subtraction (mont_mul_lazy); add/sub reduce modulo 2M; zero tests
-// accept both representatives 0 and M.  canon2 maps back to [0, M) before a value
-// is stored for code that assumes fully reduced limbs.
+// For long chains of group additions that never leave the device (the 8 x 32-bit
+// accumulation of tools/microbench/batch_affine.hip): values live in [0, 2M), so a
+// Montgomery product skips its final conditional subtraction (mont_mul_lazy); add/sub
+// reduce modulo 2M; zero tests accept both representatives 0 and M.  reduce_once maps
+// back to [0, M) before a value is stored for code that assumes fully reduced limbs.
 template <class P>
 __device__ __forceinline__ uint32_t two_m_limb(int i) {
   return (P::M[i] << 1) | (i ? P::M[i - 1] >> 31 : 0u);
@@ -749,18 +749,6 @@ __device__ __forceinline__ bool is_zero2(const Fe<P>& a) {
     m |= a.l[i] ^ P::M[i];
   }
   return z == 0 || m == 0;
-}
-template <class P>
-__device__ __forceinline__ Fe<P> canon2(const Fe<P>& a) {
-  return reduce_once(a);
-}
-__device__ __forceinline__ G1xyzz xyzz_canon2(const G1xyzz& p) {
-  G1xyzz r;
-  r.X = canon2(p.X);
-  r.Y = canon2(p.Y);
-  r.ZZ = canon2(p.ZZ);
-  r.ZZZ = canon2(p.ZZZ);
-  return r;
 }
 // madd-2008-s on [0, 2M) coordinates (p lazy or the identity, q canonical affine);
 // the same formula and special cases as xyzz_madd.

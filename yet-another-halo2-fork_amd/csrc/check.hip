@@ -68,21 +68,17 @@ __device__ __forceinline__ void sink_flush(const CheckSink& s, const WaveSink& w
 // ------------------------------------------------------------------ gates
 // A wave covers 64 consecutive rows and loops over the gates' segments there (a gate's
 // queries mostly repeat its neighbours', so the columns' lines are read once from HBM and
-// again from the cache); grid-stride over the rows.  H2G_CHECK_GATES_ON_Y = 1 (A/B builds,
-// tools/build_variant.py): one gate per blockIdx.y instead, as compress_batch_kernel's items.
-#ifndef H2G_CHECK_GATES_ON_Y
-#define H2G_CHECK_GATES_ON_Y 0
-#endif
+// again from the cache); grid-stride over the rows.  (One gate per blockIdx.y instead, as
+// compress_batch_kernel's items: measured, rejected.)
 __global__ void __launch_bounds__(EH_T) check_gates_kernel(GateCheckArgs a) {
   extern __shared__ uint4 ck_lds[];
   Fr* sl = reinterpret_cast<Fr*>(ck_lds);
   const int lane = threadIdx.x;
   const uint64_t mask = a.n - 1;
   WaveSink w;
-  const int g0 = H2G_CHECK_GATES_ON_Y ? (int)blockIdx.y : 0, g1 = H2G_CHECK_GATES_ON_Y ? g0 + 1 : a.ngates;
   for (uint64_t i = blockIdx.x * (uint64_t)EH_T + lane; i < a.n; i += (uint64_t)gridDim.x * EH_T) {
     const uint32_t kind = i < a.u ? 1u : 2u;
-    for (int g = g0; g < g1; g++) {
+    for (int g = 0; g < a.ngates; g++) {
       const Fr v = run_prog(a.prog, a.segs[g], a.consts, a.load_col, a.load_rot, i, 1, mask, Fr::zero(), sl, lane);
       sink_push(a.sink, w, !v.is_zero(), kind, (uint32_t)g, (uint32_t)i);
     }
@@ -96,9 +92,7 @@ hipError_t check_gates(const GateCheckArgs& a, hipStream_t st) {
   const size_t lds = (size_t)(a.n_slots > 0 ? a.n_slots : 1) * EH_T * sizeof(Fr);
   size_t blocks = (a.n + EH_T - 1) / EH_T;
   if (blocks > 256 * 32) blocks = 256 * 32;
-  if (H2G_CHECK_GATES_ON_Y && a.ngates > 65535) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(check_gates_kernel, dim3((unsigned)blocks, H2G_CHECK_GATES_ON_Y ? (unsigned)a.ngates : 1u),
-                     dim3(EH_T), lds, st, a);
+  hipLaunchKernelGGL(check_gates_kernel, dim3((unsigned)blocks), dim3(EH_T), lds, st, a);
   return hipGetLastError();
 }
 

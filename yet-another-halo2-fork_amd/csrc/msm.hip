@@ -89,85 +89,7 @@ __device__ __forceinline__ G1Affine ld_aff(const G1Affine* p) {
 // of a level, and DPP quad_perm broadcasts hand the results to the quad.  ~3x less
 // latency per operation for 1.3x the issue slots -- used where a kernel has too few
 // threads to fill the SIMDs.  Every lane of a quad must be active with equal operands.
-template <int K>
-__device__ __forceinline__ Fq quad_bcast(const Fq& a) {
-  Fq r;
-#pragma unroll
-  for (int i = 0; i < 8; i++)
-    r.l[i] = (uint32_t)__builtin_amdgcn_mov_dpp((int)a.l[i], K | (K << 2) | (K << 4) | (K << 6), 0xf, 0xf, false);
-  return r;
-}
-__device__ __forceinline__ Fq quad_sel(int s, const Fq& a, const Fq& b, const Fq& c, const Fq& d) {
-  // masks: a ternary chain here became an indexed load from a stack copy (scratch)
-  const uint32_t m0 = 0u - (uint32_t)(s == 0), m1 = 0u - (uint32_t)(s == 1), m2 = 0u - (uint32_t)(s == 2),
-                 m3 = 0u - (uint32_t)(s == 3);
-  Fq r;
-#pragma unroll
-  for (int i = 0; i < 8; i++) r.l[i] = (a.l[i] & m0) | (b.l[i] & m1) | (c.l[i] & m2) | (d.l[i] & m3);
-  return r;
-}
-
-// dbl-2008-s-1 (= xyzz_dbl): levels {V, X^2}, {W, S, ZZ', M^2}, {ZZZ', W Y, M (S - X')}
-__device__ G1xyzz xyzz_dbl_q4(const G1xyzz& p) {
-  if (p.is_identity()) return p;
-  const int s = threadIdx.x & 3;
-  const Fq U = dbl(p.Y);
-  const Fq a1 = (s & 1) ? p.X : U;
-  Fq m = a1 * a1;
-  const Fq V = quad_bcast<0>(m), X2 = quad_bcast<1>(m);
-  const Fq M = X2 + dbl(X2);
-  m = quad_sel(s, U, p.X, V, M) * quad_sel(s, V, V, p.ZZ, M);
-  const Fq W = quad_bcast<0>(m), S = quad_bcast<1>(m), ZZ3 = quad_bcast<2>(m), MM = quad_bcast<3>(m);
-  G1xyzz r;
-  r.X = MM - dbl(S);
-  m = quad_sel(s, W, W, M, W) * quad_sel(s, p.ZZZ, p.Y, S - r.X, p.ZZZ);
-  r.Y = quad_bcast<2>(m) - quad_bcast<1>(m);
-  r.ZZ = ZZ3;
-  r.ZZZ = quad_bcast<0>(m);
-  return r;
-}
-
-// add-2008-s (= xyzz_add): levels {U1, U2, S1, S2}, {P^2, R^2, ZZ1 ZZ2, ZZZ1 ZZZ2},
-// {PPP, Q, ZZ'}, {R (Q - X'), S1 PPP, ZZZ'}
-__device__ G1xyzz xyzz_add_q4(const G1xyzz& p, const G1xyzz& q) {
-  if (q.is_identity()) return p;
-  if (p.is_identity()) return q;
-  const int s = threadIdx.x & 3;
-  Fq m = quad_sel(s, p.X, q.X, p.Y, q.Y) * quad_sel(s, q.ZZ, p.ZZ, q.ZZZ, p.ZZZ);
-  const Fq U1 = quad_bcast<0>(m), U2 = quad_bcast<1>(m), S1 = quad_bcast<2>(m), S2 = quad_bcast<3>(m);
-  const Fq Pp = U2 - U1;
-  const Fq R = S2 - S1;
-  if (Pp.is_zero()) {
-    if (R.is_zero()) return xyzz_dbl_q4(p);
-    return G1xyzz::identity();
-  }
-  m = quad_sel(s, Pp, R, p.ZZ, p.ZZZ) * quad_sel(s, Pp, R, q.ZZ, q.ZZZ);
-  const Fq PP = quad_bcast<0>(m), RR = quad_bcast<1>(m), ZZ12 = quad_bcast<2>(m), ZZZ12 = quad_bcast<3>(m);
-  m = quad_sel(s, Pp, U1, ZZ12, Pp) * PP;
-  const Fq PPP = quad_bcast<0>(m), Q = quad_bcast<1>(m);
-  G1xyzz r;
-  r.ZZ = quad_bcast<2>(m);
-  r.X = RR - PPP - dbl(Q);
-  m = quad_sel(s, R, S1, ZZZ12, R) * quad_sel(s, Q - r.X, PPP, PPP, PPP);
-  r.Y = quad_bcast<0>(m) - quad_bcast<1>(m);
-  r.ZZZ = quad_bcast<2>(m);
-  return r;
-}
-
-__device__ G1xyzz xyzz_mul_u32_q4(const G1xyzz& p, uint32_t k) {
-  if (k == 0) return G1xyzz::identity();
-  int top = 31;
-  while (!((k >> top) & 1)) top--;
-  G1xyzz acc = p;
-  for (int b = top - 1; b >= 0; b--) {
-    acc = xyzz_dbl_q4(acc);
-    if ((k >> b) & 1) acc = xyzz_add_q4(acc, p);
-  }
-  return acc;
-}
-
-#if H2G_ACC29
-// the same quad-cooperative levels in F29 (f29.h; the back-end class, coordinates < 1.2 M)
+// The levels run in F29 (f29.h; the back-end class, coordinates < 1.2 M)
 template <int K>
 __device__ __forceinline__ F29 quad_bcast29(const F29& a) {
   F29 r;
@@ -256,18 +178,10 @@ __device__ G1xyzz29 xyzz29_mul_u32_q4(const G1xyzz29& p, uint32_t k) {
   }
   return acc;
 }
-#endif
 
 // The back-end's point type (msm_part.h RedPoint) and its operations: F29 accumulators in
-// the back-end class with H2G_ACC29, canonical G1xyzz otherwise
-__device__ __forceinline__ RedPoint rp_identity() {
-#if H2G_ACC29
-  return xyzz29_identity();
-#else
-  return G1xyzz::identity();
-#endif
-}
-#if H2G_ACC29
+// the back-end class
+__device__ __forceinline__ RedPoint rp_identity() { return xyzz29_identity(); }
 __device__ __forceinline__ RedPoint rp_add(const RedPoint& a, const RedPoint& b) { return xyzz29_add(a, b); }
 __device__ __forceinline__ RedPoint rp_dbl(const RedPoint& a) { return xyzz29_dbl(a); }
 __device__ __forceinline__ RedPoint rp_add_q4(const RedPoint& a, const RedPoint& b) { return xyzz29_add_q4(a, b); }
@@ -277,31 +191,9 @@ __device__ __forceinline__ RedPoint rp_mul_u32_q4(const RedPoint& a, uint32_t k)
 __device__ __forceinline__ G1xyzz rp_to_xyzz(const RedPoint& a) { return xyzz_from29(a); }
 // an accumulation output (bucket or boundary slot) into the back-end class
 __device__ __forceinline__ RedPoint rp_from_acc(const AccPoint& a) { return xyzz29_reduce(a); }
-#else
-__device__ __forceinline__ RedPoint rp_add(const RedPoint& a, const RedPoint& b) { return xyzz_add(a, b); }
-__device__ __forceinline__ RedPoint rp_dbl(const RedPoint& a) { return xyzz_dbl(a); }
-__device__ __forceinline__ RedPoint rp_add_q4(const RedPoint& a, const RedPoint& b) { return xyzz_add_q4(a, b); }
-__device__ __forceinline__ RedPoint rp_dbl_q4(const RedPoint& a) { return xyzz_dbl_q4(a); }
-__device__ __forceinline__ RedPoint rp_mul_u32(const RedPoint& a, uint32_t k) { return xyzz_mul_u32(a, k); }
-__device__ __forceinline__ RedPoint rp_mul_u32_q4(const RedPoint& a, uint32_t k) { return xyzz_mul_u32_q4(a, k); }
-__device__ __forceinline__ G1xyzz rp_to_xyzz(const RedPoint& a) { return a; }
-__device__ __forceinline__ RedPoint rp_from_acc(const AccPoint& a) { return a; }
-#endif
 // 16-B moves of back-end points in global memory
-__device__ __forceinline__ RedPoint ld_rp(const RedPoint* p) {
-#if H2G_ACC29
-  return ld_acc(p);
-#else
-  return *p;
-#endif
-}
-__device__ __forceinline__ void st_rp(RedPoint* p, const RedPoint& v) {
-#if H2G_ACC29
-  st_acc(p, v);
-#else
-  *p = v;
-#endif
-}
+__device__ __forceinline__ RedPoint ld_rp(const RedPoint* p) { return ld_acc(p); }
+__device__ __forceinline__ void st_rp(RedPoint* p, const RedPoint& v) { st_acc(p, v); }
 
 // Buckets spanning chunks, one thread per bucket: the piece in its first chunk t0 is
 // that chunk's last run (slot 1) unless the bucket starts the chunk (slot 0); every
@@ -310,9 +202,9 @@ __device__ __forceinline__ void st_rp(RedPoint* p, const RedPoint& v) {
 // partial sums a second pass combines per bucket (msm_big_combine_kernel): the depth
 // stays logarithmic however the scalars concentrate (fixed-base top windows: n / 2^12
 // entries per bucket at c = 22; a column of equal values: n entries per bucket).
-// (H2G_ACC29: the slots hold raw F29 accumulators, brought into the back-end class here)
+// (the slots hold raw F29 accumulators, brought into the back-end class here)
 __device__ __forceinline__ RedPoint msm_piece(const AccPoint* bnd, uint32_t t, uint32_t t0, uint32_t bs, uint32_t L) {
-  return rp_from_acc(ld_accp(bnd + 2 * (size_t)t + ((t == t0 && bs != t0 * L) ? 1 : 0)));
+  return rp_from_acc(ld_acc(bnd + 2 * (size_t)t + ((t == t0 && bs != t0 * L) ? 1 : 0)));
 }
 
 static constexpr uint32_t MSM_GROUP = 16;            // lanes per item
@@ -331,7 +223,7 @@ static size_t msm_big_items_cap(size_t nchunks) { return 2 * nchunks / MSM_ITEM 
 static size_t msm_big_multi_cap(size_t nchunks) { return 2 * nchunks / MSM_ITEM + 2; }
 
 // The item lists are reserved with one atomic per wave (a wave-level scan of the lanes'
-// item counts), not one per bucket.  Q = 4: a quad per bucket (xyzz_add_q4, ~3x less
+// item counts), not one per bucket.  Q = 4: a quad per bucket (xyzz29_add_q4, ~3x less
 // latency per addition) summing up to MSM_SMALL_Q4 pieces itself -- for small bucket
 // sets (<= 2^15), whose buckets span up to ~10 chunks of the minimum chunk length (2^16
 // points at c = 15: 9 pieces each, all of which took the big-item path: fixup 0.30 ->
@@ -377,10 +269,8 @@ msm_fixup_kernel(const AccPoint* __restrict__ bnd, const uint32_t* __restrict__ 
   ibase = __shfl(ibase, 0, 64);
   mbase = __shfl(mbase, 0, 64);
   if (b < nbt && be <= bs && lead) st_rp(buckets + b, rp_identity());  // empty (no fill of buckets[])
-#if H2G_ACC29
   // a bucket the accumulation wrote whole: its raw accumulator, into the back-end class
-  if (b < nbt && be > bs && np == 0 && lead) st_rp(buckets + b, rp_from_acc(ld_accp(whole + b)));
-#endif
+  if (b < nbt && be > bs && np == 0 && lead) st_rp(buckets + b, rp_from_acc(ld_acc(whole + b)));
   if (np == 0) return;
   if (np > small) {
     if (!cnt) return;  // the quad's other lanes
@@ -544,7 +434,7 @@ msm_rscale_kernel(const RedPoint* __restrict__ S, const RedPoint* __restrict__ R
   if (threadIdx.x == 0) part[(size_t)w * nblk + blockIdx.x] = sh[0];
 }
 
-// the same three kernels with one quad per thread above (xyzz_*_q4): a quad per group,
+// the same three kernels with one quad per thread above (xyzz29_*_q4): a quad per group,
 // 64 groups per block; taken when the groups cannot fill the SIMDs (small MSMs, e.g. the
 // 2^19-2^20-point slabs of a sharded proof), and always for the final tree
 __global__ void __launch_bounds__(MSM_THREADS)
@@ -627,26 +517,17 @@ msm_rfinal_q4_kernel(const RedPoint* __restrict__ part, uint32_t nblk, G1xyzz* _
 // The plane kernels' additions skip, wave-uniformly, when every lane adds the identity:
 // sets of small or sparse scalars (a batch of 4-bit witness columns fills 15 buckets of
 // 2^16 per set) are mostly empty groups, whose additions the identity test alone, taken
-// per lane inside the formula, does not skip for the wave.  (A/B: H2G_RED_SKIP=0.)
-#ifndef H2G_RED_SKIP
-#define H2G_RED_SKIP 1
-#endif
-__device__ __forceinline__ bool rp_is_identity(const RedPoint& a) {
-#if H2G_ACC29
-  return xyzz29_is_identity(a);
-#else
-  return a.is_identity();
-#endif
-}
+// per lane inside the formula, does not skip for the wave.
+__device__ __forceinline__ bool rp_is_identity(const RedPoint& a) { return xyzz29_is_identity(a); }
 template <int Q>
 __device__ __forceinline__ RedPoint padd(const RedPoint& a, const RedPoint& b) {
-  if (H2G_RED_SKIP && !__any(!rp_is_identity(b))) return a;
+  if (!__any(!rp_is_identity(b))) return a;
   if constexpr (Q == 4) return rp_add_q4(a, b);
   else return rp_add(a, b);
 }
 template <int Q>
 __device__ __forceinline__ RedPoint pdbl(const RedPoint& a) {
-  if (H2G_RED_SKIP && !__any(!rp_is_identity(a))) return a;
+  if (!__any(!rp_is_identity(a))) return a;
   if constexpr (Q == 4) return rp_dbl_q4(a);
   else return rp_dbl(a);
 }
@@ -880,9 +761,6 @@ void msm_free(MsmWorkspace* ws) {
     if (_e != hipSuccess) return _e;    \
   } while (0)
 
-#ifndef H2G_MSM_ADAPT  // A/B builds: 0 = the host's chunk length always (msm_chunk_len_dev off)
-#define H2G_MSM_ADAPT 1
-#endif
 uint32_t msm_chunk_len(size_t total, size_t nbt) {
   // ~4 resident waves per SIMD x 256 CUs x 64 lanes, several rounds deep ...
   uint64_t L = total / (256ull * 4 * 4 * 64 * 4);
@@ -930,7 +808,7 @@ static hipError_t msm_pipeline(const MsmScalarList& list, int nbatch, const G1Af
   // the host's chunk length; the device may pick a shorter one once the entries are
   // counted (msm_chunk_len_dev), so everything chunk-sized takes the larger count
   const uint32_t L = item_len > 0 ? item_len : msm_chunk_len(total, nb_eff);
-  const MsmChunkRule rule{L, item_len > 0 || !H2G_MSM_ADAPT ? 0u : 1u, (uint64_t)total, (uint64_t)nb_eff};
+  const MsmChunkRule rule{L, item_len > 0 ? 0u : 1u, (uint64_t)total, (uint64_t)nb_eff};
   const size_t nchunks = msm_chunk_cap(rule);
   const uint32_t m1 = (NB + RG - 1) / RG;
   const bool red_q4 = (size_t)m1 * WB <= RED_Q4_MAX;
@@ -978,9 +856,9 @@ static hipError_t msm_pipeline(const MsmScalarList& list, int nbatch, const G1Af
   while ((1ull << key_bits) < (uint64_t)nbt) key_bits++;
   int fb = key_bits < 10 ? key_bits : 10;
   while (fb < FB_MAX && (((uint64_t)nbt + (1ull << fb) - 1) >> fb) > COARSE_MAX) fb++;
-  // ent (the coarse-binned entries) is dead once the partition has run: with H2G_ACC29 it
-  // holds the accumulation's whole buckets (raw F29) until the fixup converts them
-  const size_t whole_bytes = H2G_ACC29 ? (size_t)nbt * sizeof(AccPoint) : 0;
+  // ent (the coarse-binned entries) is dead once the partition has run: it then holds the
+  // accumulation's whole buckets (raw F29) until the fixup converts them
+  const size_t whole_bytes = (size_t)nbt * sizeof(AccPoint);
   const Need need[10] = {{&ws->ent, std::max(total * 8, whole_bytes)},
                          {&ws->vals_out, total * 4},
                          {&ws->item_bucket, icap * sizeof(MsmBigItem)},    // big-bucket items
@@ -1007,7 +885,7 @@ static hipError_t msm_pipeline(const MsmScalarList& list, int nbatch, const G1Af
   RedPoint* ipart = (RedPoint*)ws->total_items;
   RedPoint* buckets = (RedPoint*)ws->buckets;
   AccPoint* bnd = (AccPoint*)ws->partials;
-  AccPoint* whole = H2G_ACC29 ? (AccPoint*)ws->ent : (AccPoint*)buckets;  // the accumulation's whole buckets
+  AccPoint* whole = (AccPoint*)ws->ent;  // the accumulation's whole buckets
   RedPoint* rS = (RedPoint*)ws->segs;  // rscale scheme: group sums, group weights, block sums
   RedPoint* rR = rS + (size_t)WB * m1;
   RedPoint* rP = rR + (size_t)WB * m1;

@@ -1,6 +1,6 @@
 // msm_acc.hip -- step 3 of the MSM pipeline (msm.hip) for gfx950: the bucket accumulation,
-// the dominant kernel of create_proof.  Its own translation unit so that A/B builds of it
-// (tools/build_variant.py) recompile one kernel, not the reduction's dozen.
+// the dominant kernel of create_proof.  Its own translation unit so that variant builds of
+// it (tools/build_variant.py) recompile one kernel, not the reduction's dozen.
 #include "msm_part.h"
 
 namespace h2g {
@@ -26,40 +26,26 @@ __device__ __forceinline__ G1Affine ld_aff(const G1Affine* p) {
 // is the whole bucket iff the bucket starts and ends inside the chunk: such buckets are
 // written directly, a run that crosses a chunk boundary goes to the chunk's boundary
 // slot (slot 0 = its first run, slot 1 = its last run) for the fixup.
-// H2G_ACC29: the accumulator is F29 (f29.h) and is stored raw -- a run end is a handful of
+// The accumulator is F29 (f29.h) and is stored raw -- a run end is a handful of
 // stores, not a conversion: some lane of a wave ends a run on most steps, so anything
 // costlier there would be paid by the whole wave nearly every step.
 __device__ __forceinline__ void msm_emit(uint32_t key, const AccPoint& acc, bool first, bool from_prev, bool to_next,
                                          uint32_t t, AccPoint* __restrict__ buckets, AccPoint* __restrict__ bnd) {
   AccPoint* dst = (!from_prev && !to_next) ? buckets + key : bnd + 2 * (size_t)t + (first ? 0 : 1);
-#if H2G_ACC29
   st_acc(dst, acc);
-#else
-  *dst = xyzz_canon2(acc);  // lazy [0, 2M) -> fully reduced for the later kernels
-#endif
 }
 
-__device__ __forceinline__ AccPoint acc_identity() {
-#if H2G_ACC29
-  return xyzz29_identity();
-#else
-  return G1xyzz::identity();
-#endif
-}
+__device__ __forceinline__ AccPoint acc_identity() { return xyzz29_identity(); }
 template <bool SAFE>
 __device__ __forceinline__ AccPoint acc_madd(const AccPoint& acc, const G1Affine& pt, bool* dbl) {
-#if H2G_ACC29
   if (pt.is_identity()) return acc;
   return xyzz29_madd<SAFE>(acc, to29(pt.x), to29(pt.y), dbl);
-#else
-  (void)dbl;
-  return xyzz_madd_lazy(acc, pt);
-#endif
 }
 
 // one chunk [t L, t L + L) of the sorted values: the runs it holds to their buckets or to
 // its boundary slots.  SAFE = false: the mixed addition without its doubling branch (the
-// hot loop at 4 waves per SIMD); returns true when a run met p == q, and the chunk must be
+// hot loop at 4 waves per SIMD; with the doubling branch inside it: 152 VGPRs, 3 waves per
+// SIMD -- measured, rejected); returns true when a run met p == q, and the chunk must be
 // redone with SAFE = true -- its writes go to the same places, every one of them rewritten.
 // The next entry's base point is loaded before the current mixed addition (software-
 // pipelined gather), so its latency hides behind ~3000 VALU ops.
@@ -119,9 +105,6 @@ __device__ __forceinline__ bool acc_chunk(uint32_t t, const G1Affine* __restrict
   return dbl;
 }
 
-#ifndef H2G_ACC_FAST  // 0: the doubling branch inside the hot loop (152 VGPRs, 3 waves per SIMD; A/B)
-#define H2G_ACC_FAST 1
-#endif
 // the chunks whose runs met p == q (same point twice in a row of one bucket: repeated bases
 // of a generic MSM; never for distinct SRS points), recorded for the repair pass:
 // rep[0] = count, rep[1 ..] = chunk ids (up to MSM_REPAIR_CAP; beyond it every chunk is redone)
@@ -130,7 +113,7 @@ msm_acc_kernel(const G1Affine* __restrict__ bases, const uint32_t* __restrict__ 
                const uint32_t* __restrict__ koff, uint32_t nbt, const uint32_t* __restrict__ d_total,
                AccPoint* __restrict__ buckets, AccPoint* __restrict__ bnd, uint32_t* __restrict__ rep) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (acc_chunk<!H2G_ACC29 || !H2G_ACC_FAST>(t, bases, vals, koff, nbt, d_total[0], d_total[1], buckets, bnd)) {
+  if (acc_chunk<false>(t, bases, vals, koff, nbt, d_total[0], d_total[1], buckets, bnd)) {
     const uint32_t i = atomicAdd(rep, 1u);
     if (i < MSM_REPAIR_CAP) rep[1 + i] = t;
   }
@@ -161,9 +144,8 @@ hipError_t msm_accumulate(const G1Affine* bases, const uint32_t* vals, const uin
   const int T = MSM_THREADS;
   const unsigned cgrid = (unsigned)((nchunks_cap + T - 1) / T);
   hipLaunchKernelGGL(msm_acc_kernel, dim3(cgrid), dim3(T), 0, st, bases, vals, koff, nbt, d_total, buckets, bnd, rep);
-  if (H2G_ACC29)
-    hipLaunchKernelGGL(msm_acc_repair_kernel, dim3(MSM_REPAIR_BLOCKS), dim3(T), 0, st, bases, vals, koff, nbt,
-                       d_total, buckets, bnd, (const uint32_t*)rep);
+  hipLaunchKernelGGL(msm_acc_repair_kernel, dim3(MSM_REPAIR_BLOCKS), dim3(T), 0, st, bases, vals, koff, nbt, d_total,
+                     buckets, bnd, (const uint32_t*)rep);
   return hipGetLastError();
 }
 

@@ -101,21 +101,11 @@ struct MsmPartArgs {
 };
 hipError_t msm_partition(const MsmPartArgs& a, hipStream_t st, MsmPhaseEvents* prof);
 
-// The accumulation's arithmetic: 1 = F29 (f29.h: 9 x 29-bit limbs, no carry ops in the
-// products); its buckets and boundary slots are then raw G1xyzz29 accumulators (144 B),
-// converted to canonical G1xyzz by the fixup.  0 = the 8 x 32-bit FIPS arithmetic of
-// bn254.h writing G1xyzz directly (A/B builds: tools/build_variant.py TAG --src
-// msm_acc.hip,msm.hip -DH2G_ACC29=0).
-#ifndef H2G_ACC29
-#define H2G_ACC29 1
-#endif
-#if H2G_ACC29
+// The accumulation's arithmetic is F29 (f29.h: 9 x 29-bit limbs, no carry ops in the
+// products); its buckets and boundary slots are raw G1xyzz29 accumulators (144 B),
+// converted to canonical G1xyzz by the fixup.
 using AccPoint = G1xyzz29;
 using RedPoint = G1xyzz29;  // the fixup's and the reduction's points (f29.h's back-end class)
-#else
-using AccPoint = G1xyzz;
-using RedPoint = G1xyzz;
-#endif
 
 // raw 16-B moves of the accumulators (G1xyzz29 is 9 x 16 B)
 __device__ __forceinline__ void st_acc(G1xyzz29* dst, const G1xyzz29& v) {
@@ -139,14 +129,6 @@ __device__ __forceinline__ G1xyzz29 ld_acc(const G1xyzz29* src) {
   return v;
 }
 __device__ __forceinline__ G1xyzz acc_to_xyzz(const G1xyzz29& v) { return xyzz_from29(v); }
-__device__ __forceinline__ G1xyzz acc_to_xyzz(const G1xyzz& v) { return v; }
-__device__ __forceinline__ AccPoint ld_accp(const AccPoint* p) {
-#if H2G_ACC29
-  return ld_acc(p);
-#else
-  return *p;
-#endif
-}
 
 // step 3 of the pipeline (msm_acc.hip): XYZZ accumulation of the bucket-sorted values in
 // chunks of L = d_total[1] (d_total[0]: the entries), one thread per chunk (a grid for

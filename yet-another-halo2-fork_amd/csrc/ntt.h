@@ -31,10 +31,10 @@ struct NttTables {
   // the F29 passes' in-pass twiddles w_64^j, j < 32, as F29 elements packed in 8 x 32 bits
   // (a 2^m-point pass reads every 2^(6-m)-th); L >= 6
   Fr* root64 = nullptr;
-  // lo / hi as packed F29 elements (passes that form their inter-pass twiddles from the
-  // two-level table instead of streaming pass_tw, H2G_NTT_TW_LIVE)
-  Fr* lo29 = nullptr;
-  Fr* hi29 = nullptr;
+  // Unused (two table pointers of a rejected pass variant lived here).  NttTables is a
+  // by-value kernel argument: without these 16 bytes the argument offsets in 16 of the
+  // NTT kernels move.  Drop them with the next change to those kernels.
+  Fr* reserved[2] = {nullptr, nullptr};
   // the constant multiplied into the first pass's table (pass_tw; a transform's scale, so
   // its last pass needs no product) and its inverse (divided out of a call's epilogue)
   Fr fold = Fr::one();

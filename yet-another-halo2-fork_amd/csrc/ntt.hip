@@ -17,8 +17,8 @@
 // radix-8 round on the top 3 index bits, (m-3) lane<->register bit swaps by
 // __shfl_xor (no LDS staging, no barriers), and a second in-register round on
 // the low m-3 bits.  Global accesses are runs of >= 8 x 32 B across the lanes
-// of one instruction.  Inter-pass twiddles come from a 2-level table
-// w^E = lo[E mod 2^b] * hi[E >> b] (both L2-resident).
+// of one instruction.  Inter-pass twiddles are streamed from per-pass tables
+// (NttTables::pass_tw), built once from a 2-level table w^E = lo[E mod 2^b] * hi[E >> b].
 #include <algorithm>
 #include <type_traits>
 
@@ -57,20 +57,6 @@ __device__ __forceinline__ Fr twiddle(const NttTables& t, uint64_t e) {
   return t.lo[e & ((1ull << t.b) - 1)] * t.hi[e >> t.b];
 }
 
-__device__ __forceinline__ Fr shfl_xor_fr(const Fr& v, int mask) {
-  Fr r;
-#pragma unroll
-  for (int i = 0; i < 8; i++) r.l[i] = (uint32_t)__shfl_xor((int)v.l[i], mask);
-  return r;
-}
-
-__device__ __forceinline__ Fr fr_select(int c, const Fr& a, const Fr& b) {
-  Fr r;
-#pragma unroll
-  for (int i = 0; i < 8; i++) r.l[i] = c ? a.l[i] : b.l[i];
-  return r;
-}
-
 // y mod 3 for 64-bit y with 32-bit arithmetic (2^32 = 1 mod 3)
 __device__ __forceinline__ uint32_t mod3(uint64_t y) {
   return ((uint32_t)(y >> 32) % 3u + (uint32_t)y % 3u) % 3u;
@@ -78,228 +64,8 @@ __device__ __forceinline__ uint32_t mod3(uint64_t y) {
 
 __device__ __forceinline__ uint32_t brev_bits(uint32_t x, int m) { return __brev(x) >> (32 - m); }
 
-// Butterfly arithmetic on lazily reduced values (bn254.h's [0, 2M) arithmetic): the
-// passes keep their data in [0, 2M) -- sums reduce modulo 2M, a difference headed for a
-// product is a - b + 2M in (0, 4M) without any select, and the products skip their final
-// subtraction (an input < 4M times a twiddle < M gives < 2M); only the last pass's stores
-// reduce to [0, M).  ~24 VALU ops fewer per multiplied butterfly.
-#ifndef H2G_NTT_LAZY  // A/B builds: 0 = fully reduced butterflies
-#define H2G_NTT_LAZY 1
-#endif
-__device__ __forceinline__ Fr bf_add(const Fr& a, const Fr& b) {
-  if constexpr (H2G_NTT_LAZY) return add2(a, b);
-  else return a + b;
-}
-__device__ __forceinline__ Fr bf_sub(const Fr& a, const Fr& b) {  // a difference kept as is
-  if constexpr (H2G_NTT_LAZY) return sub2(a, b);
-  else return a - b;
-}
-__device__ __forceinline__ Fr bf_sub_mul(const Fr& a, const Fr& b, const Fr& w) {  // (a - b) w
-  if constexpr (H2G_NTT_LAZY) {
-    Fr d;
-    unsigned br = 0, c = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) d.l[i] = __builtin_subc(a.l[i], b.l[i], br, &br);
-#pragma unroll
-    for (int i = 0; i < 8; i++) d.l[i] = __builtin_addc(d.l[i], two_m_limb<FrParams>(i), c, &c);  // (0, 4M)
-    return mont_mul_lazy(d, w);
-  } else {
-    return (a - b) * w;
-  }
-}
-__device__ __forceinline__ Fr bf_mul(const Fr& x, const Fr& w) {  // x < 2M, w < M
-  if constexpr (H2G_NTT_LAZY) return mont_mul_lazy(x, w);
-  else return x * w;
-}
-__device__ __forceinline__ Fr bf_out(const Fr& x) {  // to [0, M) for the stored result
-  if constexpr (H2G_NTT_LAZY) return reduce_once(x);
-  else return x;
-}
-
-// In-register DIF of 2^M-point columns.  Lane = c + CPW * rg; register q of the
-// lane initially holds row r = rg + LPC * q.  `w[j] = w_{2^M}^j`, j < 2^(M-1).
-// After run(), register q holds DIF position rpos(q, rg) (output index
-// k = bitrev_M(rpos)).
-template <int M>
-struct WaveDif {
-  static constexpr int LPC = 1 << (M - 3);  // lanes per column
-  static constexpr int CPW = 64 / LPC;      // columns per wave
-
-  __device__ static __forceinline__ void run(Fr x[8], const Fr* w, int rg) {
-    // round A: row bits M-1..M-3 live in the register index
-#pragma unroll
-    for (int t = 2; t >= 0; t--) {
-      const int htlog = (M - 3) + t;
-#pragma unroll
-      for (int p = 0; p < 4; p++) {
-        const int q = ((p >> t) << (t + 1)) | (p & ((1 << t) - 1));
-        const int j = rg + (p & ((1 << t) - 1)) * LPC;
-        const Fr a = x[q], b = x[q + (1 << t)];
-        x[q] = bf_add(a, b);
-        x[q + (1 << t)] = bf_sub_mul(a, b, w[j << (M - 1 - htlog)]);
-      }
-    }
-    // swap register bit b <-> lane bit b (lane index bit log2(CPW) + b), b < M-3
-#pragma unroll
-    for (int b = 0; b < M - 3; b++) {
-      const int lb = (rg >> b) & 1;
-#pragma unroll
-      for (int p = 0; p < 4; p++) {
-        const int q = ((p >> b) << (b + 1)) | (p & ((1 << b) - 1));
-        // value selects only (a data-dependent register index would spill x[] to scratch)
-        const Fr lo_v = x[q], hi_v = x[q | (1 << b)];
-        const Fr recv = shfl_xor_fr(fr_select(lb, lo_v, hi_v), CPW << b);
-        x[q] = fr_select(lb, recv, lo_v);
-        x[q | (1 << b)] = fr_select(lb, hi_v, recv);
-      }
-    }
-    // round B: row bits M-4..0 now live in register bits M-4..0
-#pragma unroll
-    for (int t = M - 4; t >= 0; t--) {
-#pragma unroll
-      for (int p = 0; p < 4; p++) {
-        const int q = ((p >> t) << (t + 1)) | (p & ((1 << t) - 1));
-        const int j = q & ((1 << t) - 1);  // compile-time after unrolling
-        const Fr a = x[q], b = x[q + (1 << t)];
-        x[q] = bf_add(a, b);
-        // w^0 = 1 exactly (Montgomery one, fully reduced): skip the product --
-        // every butterfly of the t = 0 stage, half of t = 1, a quarter of t = 2
-        x[q + (1 << t)] = j == 0 ? bf_sub(a, b) : bf_sub_mul(a, b, w[j << (M - 1 - t)]);
-      }
-    }
-  }
-
-  // DIF position held by register q of lane rg after run()
-  __device__ static __forceinline__ uint32_t rpos(int q, int rg) {
-    constexpr int LB = M - 3;
-    const uint32_t lowmask = (1u << LB) - 1;
-    const uint32_t lo = (uint32_t)q & lowmask;                              // row bits < LB
-    const uint32_t mid = (uint32_t)rg & lowmask;                            // row bits LB..2LB-1
-    const uint32_t hi = ((uint32_t)q >> LB) << LB;                          // untouched register bits
-    return lo + ((mid | hi) << LB);
-  }
-};
-
 // ---------------------------------------------------------------------------
-// Generic (non-last) pass, 2^M-point sub-transforms, in place on `data`.
-//   L_p = 2^lrem (remaining length including this pass), S = L_p / 2^M.
-//   Pass 0 reads `in` (n_in valid elements, zero padding beyond) and, if
-//   `distribute`, multiplies element i by zeta^(i mod 3) (domain.rs:325-341).
-template <int M>
-__global__ void __launch_bounds__(NTT_THREADS, NttPassWaves<M>::value)
-ntt_pass_kernel(Fr* data, NttIo io, int first, uint64_t n_in, NttTables tab, const Fr* __restrict__ ptw, int L,
-                int lrem, int distribute, Fr z1, Fr z2) {
-  using D = WaveDif<M>;
-  data += (uint64_t)blockIdx.y << L;  // transform blockIdx.y of a batch
-  const Fr* in = first ? io.src[blockIdx.y] : nullptr;
-  __shared__ Fr w[1 << (M - 1)];
-  for (int j = threadIdx.x; j < (1 << (M - 1)); j += blockDim.x) w[j] = twiddle(tab, (uint64_t)j << (L - M));
-  __syncthreads();
-  const int lane = threadIdx.x & 63;
-  const uint64_t wave = (uint64_t)blockIdx.x * NTT_WAVES + (threadIdx.x >> 6);
-  if (wave >= (1ull << L) / ((1ull << M) * D::CPW)) return;
-  const uint64_t S = 1ull << (lrem - M);
-  const uint64_t groups = S / D::CPW;
-  const uint64_t q = wave / groups;
-  const uint64_t g = wave % groups;
-  const uint64_t base = (q << lrem) + g * D::CPW;
-  const int c = lane % D::CPW, rg = lane / D::CPW;
-  Fr x[8];
-#pragma unroll
-  for (int qq = 0; qq < 8; qq++) {
-    const uint64_t pos = base + c + (uint64_t)(rg + D::LPC * qq) * S;
-    if (in) {
-      if (pos < n_in) {
-        Fr v = ld_fr(in + pos);
-        if (distribute) {
-          const uint32_t md = mod3(pos);
-          v = v * fr_select(md == 1, z1, fr_select(md == 2, z2, Fr::one()));
-        }
-        x[qq] = v;
-      } else {
-        x[qq] = Fr::zero();
-      }
-    } else {
-      x[qq] = ld_fr(data + pos);
-    }
-  }
-  D::run(x, w, rg);
-  const uint64_t ilow = g * D::CPW + c;
-#pragma unroll
-  for (int qq = 0; qq < 8; qq++) {
-    const uint32_t k = brev_bits(D::rpos(qq, rg), M);
-    // w^((N / L_p) i_low k) from the precomputed pass table (one load instead of a
-    // table product + multiplication)
-    const Fr v = bf_mul(x[qq], ld_fr(ptw + (uint64_t)k * S + ilow));
-    st_fr(data + base + c + (uint64_t)k * S, v);
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Last pass (2^6-point columns): contiguous runs, output in natural order.
-//   pos = k_0 (N/N_0) + m_idx 2^6 + i ;  y = k_0 + mid_nat(m_idx) + (N/2^6) k
-//   Epilogue: multiply by `scale` and, if `distribute`, by the zeta power of
-//   y mod 3; drop y >= out_len (truncation, domain.rs:288-290).
-__global__ void __launch_bounds__(NTT_THREADS, NTT_MIN_WAVES)
-ntt_last_kernel(const Fr* data, NttIo io, uint64_t out_len, NttTables tab, int L, NttPlanLg plan, int has_mul,
-                Fr mul0, Fr mul1, Fr mul2) {
-  constexpr int M = 6;
-  data += (uint64_t)blockIdx.y << L;
-  Fr* out = io.dst[blockIdx.y];
-  using D = WaveDif<M>;
-  __shared__ Fr w[1 << (M - 1)];
-  for (int j = threadIdx.x; j < (1 << (M - 1)); j += blockDim.x) w[j] = twiddle(tab, (uint64_t)j << (L - M));
-  __syncthreads();
-  const int* lgs = plan.lg;
-  const int P = plan.p;
-  const int lane = threadIdx.x & 63;
-  const uint64_t wave = (uint64_t)blockIdx.x * NTT_WAVES + (threadIdx.x >> 6);
-  if (wave >= (1ull << L) / ((1ull << M) * D::CPW)) return;
-  const int l0 = lgs[0];
-  const uint64_t groups = (1ull << l0) / D::CPW;
-  const uint64_t midx = wave / groups;
-  const uint64_t g = wave % groups;
-  // m_idx = k_1 (N_2..N_{P-2}) + ... + k_{P-2}  ->  natural weight of k_p is N_0..N_{p-1}
-  uint64_t mid_nat = 0;
-  {
-    uint64_t rem = midx;
-    int wbits_tail = L - M;  // bits of k_0..k_{P-2}
-#pragma unroll
-    for (int p = NTT_MAX_PASSES - 2; p >= 1; p--) {  // constant indices into plan.lg (no scratch copy)
-      if (p > P - 2) continue;
-      const int lgp = lgs[p];
-      const uint64_t dig = rem & ((1ull << lgp) - 1);
-      rem >>= lgp;
-      wbits_tail -= lgp;
-      mid_nat |= dig << wbits_tail;
-    }
-  }
-  const int c = lane % D::CPW, rg = lane / D::CPW;
-  const uint64_t k0 = g * D::CPW + c;
-  const uint64_t colbase = k0 * (1ull << (L - l0)) + (midx << M);
-  Fr x[8];
-#pragma unroll
-  for (int qq = 0; qq < 8; qq++) x[qq] = ld_fr(data + colbase + rg + D::LPC * qq);
-  D::run(x, w, rg);
-  const uint64_t kstride = 1ull << (L - M);
-#pragma unroll
-  for (int qq = 0; qq < 8; qq++) {
-    const uint32_t k = brev_bits(D::rpos(qq, rg), M);
-    const uint64_t y = k0 + mid_nat + (uint64_t)k * kstride;
-    if (y >= out_len) continue;
-    Fr v = x[qq];
-    if (has_mul) {  // ifft divisor and/or zeta power, one product (host folds them)
-      const uint32_t md = mod3(y);
-      v = v * fr_select(md == 1, mul1, fr_select(md == 2, mul2, mul0));  // < 2M in, reduced out
-    } else {
-      v = bf_out(v);
-    }
-    st_fr(out + y, v);
-  }
-}
-
-// ---------------------------------------------------------------------------
-// The passes in 9 x 29-bit limbs (f29.h), H2G_NTT29.  The transform is linear, so the
+// The passes run in 9 x 29-bit limbs (f29.h).  The transform is linear, so the
 // stored integers move in and out by repacking only (f29.h: raw29 / pack29) and the
 // constants -- twiddles, coset powers, scales -- are F29 elements (the pass tables are
 // built in that form, storage_to_f29_packed).  Products are f29.h's carry-free REDC.
@@ -307,9 +73,6 @@ ntt_last_kernel(const Fr* data, NttIo io, uint64_t out_len, NttTables tab, int L
 // subtracts with K_s = 2^(s+2) M (>= the stage's input bound with a top-limb margin), so
 // after 6 stages every value is < 254 M < 2^262 and the closing product (pass twiddle or
 // epilogue constant, < M) brings it back below 2.6 M; the last pass reduces to [0, M).
-#ifndef H2G_NTT29  // A/B builds: 0 = the 8 x 32-bit FIPS passes above
-#define H2G_NTT29 1
-#endif
 
 __device__ __forceinline__ F29 ld29(const Fr* p) { return raw29(ld_fr(p)); }
 __device__ __forceinline__ void st29(Fr* p, const F29& v) { st_fr(p, pack29<FrParams>(v)); }
@@ -342,13 +105,16 @@ __device__ __forceinline__ F29 nsub29(const F29& a, const F29& b) {
   return sub29<FrParams, (4u << S), 29>(a, b);
 }
 
-// The same butterfly schedule as WaveDif<M>::run (lane / register layout, rpos), its
-// stages as templates: unrolled loops over whole products were left rolled by the
-// compiler, and a rolled stage loop indexes x[] at run time (x[] then lives in scratch).
+// In-register DIF of 2^M-point columns.  Lane = c + CPW * rg; register q of the
+// lane initially holds row r = rg + LPC * q.  `w[j] = w_{2^M}^j`, j < 2^(M-1).
+// After run(), register q holds DIF position rpos(q, rg) (output index
+// k = bitrev_M(rpos)).  The stages are templates: unrolled loops over whole products were
+// left rolled by the compiler, and a rolled stage loop indexes x[] at run time (x[] then
+// lives in scratch).
 template <int M>
 struct WaveDif29 {
-  static constexpr int LPC = 1 << (M - 3);
-  static constexpr int CPW = 64 / LPC;
+  static constexpr int LPC = 1 << (M - 3);  // lanes per column
+  static constexpr int CPW = 64 / LPC;      // columns per wave
   template <int T>  // round A, row bit M-3+T (stage 2 - T)
   __device__ static __forceinline__ void stage_a(F29 x[8], const F29* w, int rg) {
     constexpr int htlog = (M - 3) + T;
@@ -397,6 +163,16 @@ struct WaveDif29 {
     swap_bits<0>(x, rg);
     stage_b<M - 4>(x, w);
   }
+
+  // DIF position held by register q of lane rg after run()
+  __device__ static __forceinline__ uint32_t rpos(int q, int rg) {
+    constexpr int LB = M - 3;
+    const uint32_t lowmask = (1u << LB) - 1;
+    const uint32_t lo = (uint32_t)q & lowmask;                              // row bits < LB
+    const uint32_t mid = (uint32_t)rg & lowmask;                            // row bits LB..2LB-1
+    const uint32_t hi = ((uint32_t)q >> LB) << LB;                          // untouched register bits
+    return lo + ((mid | hi) << LB);
+  }
 };
 
 // the constants of one launch in F29 form (host-converted)
@@ -405,13 +181,9 @@ struct NttConst29 {
   F29 mul[3];      // epilogue multiplier per y mod 3 (last pass), one29 when none
 };
 
-// inter-pass twiddles formed in the pass from the two-level table (one product and two
-// L2-resident loads per element) instead of streamed from pass_tw (32 B of HBM per element):
-// 1 = the first pass only (its table is N entries), 2 = every non-last pass, 0 = none
-#ifndef H2G_NTT_TW_LIVE
-#define H2G_NTT_TW_LIVE 0
-#endif
-
+// (Inter-pass twiddles formed in the pass from the two-level table -- one product and two
+// L2-resident loads per element -- instead of streamed from pass_tw, 32 B of HBM per
+// element: measured, rejected.)
 template <int M>
 __global__ void __launch_bounds__(NTT_THREADS, NttPassWaves<M>::value)
 ntt_pass29_kernel(Fr* data, NttIo io, int first, uint64_t n_in, NttTables tab, const Fr* __restrict__ ptw, int L,
@@ -453,28 +225,18 @@ ntt_pass29_kernel(Fr* data, NttIo io, int first, uint64_t n_in, NttTables tab, c
   });
   D::run(x, w, rg);
   const uint64_t ilow = g * D::CPW + c;
-  const bool live = H2G_NTT_TW_LIVE == 2 || (H2G_NTT_TW_LIVE == 1 && first);
   sfor<0, 8>([&](auto qc) {
     constexpr int qq = decltype(qc)::value;
-    const uint32_t k = brev_bits(WaveDif<M>::rpos(qq, rg), M);
-    F29 tw;
-    if (live) {  // w^((N / L_p) i_low k) = lo[e mod 2^b] hi[e >> b], < 1.01 M
-      const uint64_t e = (ilow * k) << (L - lrem);
-      tw = mul29<FrParams>(ld29(tab.lo29 + (e & ((1ull << tab.b) - 1))), ld29(tab.hi29 + (e >> tab.b)));
-    } else {
-      tw = ld29(ptw + (uint64_t)k * S + ilow);
-    }
+    const uint32_t k = brev_bits(D::rpos(qq, rg), M);
+    const F29 tw = ld29(ptw + (uint64_t)k * S + ilow);
     st29(data + base + c + (uint64_t)k * S, mul29<FrParams>(x[qq], tw));
   });
 }
 
-// Persistent variant of ntt_pass29_kernel for the passes after the first (H2G_NTT_PIPE): a wave walks column groups
-// item, item + stride, ... and loads the next group's elements before it transforms the
-// current one, so a SIMD's VALU work is not held up by its waves' loads all arriving at
-// once (one launch round of the plain kernel loads, then computes, then stores).
-#ifndef H2G_NTT_PIPE
-#define H2G_NTT_PIPE 1
-#endif
+// Persistent variant of ntt_pass29_kernel for the passes after the first: a wave walks
+// column groups item, item + stride, ... and loads the next group's elements before it
+// transforms the current one, so a SIMD's VALU work is not held up by its waves' loads all
+// arriving at once (one launch round of the plain kernel loads, then computes, then stores).
 template <int M>
 __global__ void __launch_bounds__(NTT_THREADS, 2)
 ntt_pass29p_kernel(Fr* data, NttTables tab, const Fr* __restrict__ ptw, int L, int lrem, uint64_t items) {
@@ -517,7 +279,7 @@ ntt_pass29p_kernel(Fr* data, NttTables tab, const Fr* __restrict__ ptw, int L, i
     const uint64_t ilow = (cur % groups) * D::CPW + c;
     sfor<0, 8>([&](auto qc) {
       constexpr int qq = decltype(qc)::value;
-      const uint32_t k = brev_bits(WaveDif<M>::rpos(qq, rg), M);
+      const uint32_t k = brev_bits(D::rpos(qq, rg), M);
       st29(data + base + c + (uint64_t)k * S, mul29<FrParams>(x[qq], ld29(ptw + (uint64_t)k * S + ilow)));
     });
     if (!more) break;
@@ -529,9 +291,6 @@ ntt_pass29p_kernel(Fr* data, NttTables tab, const Fr* __restrict__ ptw, int L, i
 // circuit): y_k = x_0 + w_8^k x_1 (w_8^(k+4) = -w_8^k), two loads and three products per
 // column instead of eight loads and the twelve products of the 8-point DIF.  One lane per
 // column; outputs < 1.04 M.
-#ifndef H2G_NTT_SPARSE
-#define H2G_NTT_SPARSE 1
-#endif
 __global__ void __launch_bounds__(NTT_THREADS)
 ntt_first_sparse29_kernel(Fr* data, NttIo io, uint64_t n_in, NttTables tab, const Fr* __restrict__ ptw, int L,
                           int distribute, NttConst29 k29) {
@@ -634,7 +393,7 @@ ntt_last29_kernel(const Fr* data, NttIo io, uint64_t out_len, NttTables tab, int
   const uint64_t kstride = 1ull << (L - M);
   sfor<0, 8>([&](auto qc) {
     constexpr int qq = decltype(qc)::value;
-    const uint32_t k = brev_bits(WaveDif<M>::rpos(qq, rg), M);
+    const uint32_t k = brev_bits(D::rpos(qq, rg), M);
     const uint64_t y = k0 + mid_nat + (uint64_t)k * kstride;
     if (!TRUNC || y < out_len) {
       if constexpr (ONE) {
@@ -719,14 +478,7 @@ __global__ void ntt_root64_kernel(Fr* out, NttTables tab, int L) {
   if (j < 32) out[j] = storage_to_f29_packed<FrParams>(twiddle(tab, (uint64_t)j << (L - 6)));
 }
 
-// lo / hi as packed F29 elements
-__global__ void ntt_tables29_kernel(Fr* lo29, Fr* hi29, const Fr* lo, const Fr* hi, uint64_t nlo, uint64_t nhi) {
-  const uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-  if (t < nlo) lo29[t] = storage_to_f29_packed<FrParams>(lo[t]);
-  if (t < nhi) hi29[t] = storage_to_f29_packed<FrParams>(hi[t]);
-}
-
-// pass table: t = k * S + i_low over [0, 2^lrem): w^(i_low k 2^(L - lrem))
+// pass table: t = k * S + i_low over [0, 2^lrem): w^(i_low k 2^(L - lrem)), packed F29
 __global__ void ntt_pass_tw_kernel(Fr* out, NttTables tab, int L, int lrem, int M, int fold) {
   const uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
   if (t >= (1ull << lrem)) return;
@@ -734,7 +486,7 @@ __global__ void ntt_pass_tw_kernel(Fr* out, NttTables tab, int L, int lrem, int 
   const uint64_t k = t / S, ilow = t % S;
   Fr v = twiddle(tab, (ilow * k) << (L - lrem));
   if (fold) v = v * tab.fold;  // the first pass carries the transform's scale
-  out[t] = H2G_NTT29 ? storage_to_f29_packed<FrParams>(v) : v;  // the passes' form
+  out[t] = storage_to_f29_packed<FrParams>(v);  // the passes' form
 }
 
 // ---------------------------------------------------------------------------
@@ -749,14 +501,8 @@ void ntt_split(int L, int* P, int lg[NTT_MAX_PASSES]) {
   int p = (L + 5) / 6;
   const int R = L - 6 * (p - 1);
   int i = 0;
-#ifndef H2G_NTT_SPLIT  // A/B: 0 = the short pass first, 1 = second, 2 = two 5-bit passes for a 4-bit one
-#define H2G_NTT_SPLIT 0
-#endif
-  if (H2G_NTT_SPLIT == 2 && R == 4 && p >= 3) {
-    lg[i++] = 5;
-    lg[i++] = 5;
-  } else if (R >= 3) {
-    if (H2G_NTT_SPLIT == 1 && p >= 3) lg[i++] = 6;
+  // the short pass goes first (second, or two 5-bit passes for a 4-bit one: measured, rejected)
+  if (R >= 3) {
     lg[i++] = R;
   } else {  // borrow 3 bits so every pass has 3..6 bits
     lg[i++] = 3;
@@ -797,12 +543,6 @@ hipError_t ntt_build_tables(NttTables* t, const Fr& omega, int L, hipStream_t st
   e = hipMalloc(&t->root64, 32 * sizeof(Fr));
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(ntt_root64_kernel, dim3(1), dim3(32), 0, st, t->root64, *t, L);
-  e = hipMalloc(&t->lo29, nlo * sizeof(Fr));
-  if (e != hipSuccess) return e;
-  e = hipMalloc(&t->hi29, (nhi > 0 ? nhi : 1) * sizeof(Fr));
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(ntt_tables29_kernel, dim3((unsigned)((mx + bs - 1) / bs)), dim3(bs), 0, st, t->lo29, t->hi29,
-                     t->lo, t->hi, nlo, nhi);
   lrem = L;
   for (int p = 0; p < P - 1; p++) {
     const uint64_t cnt = 1ull << lrem;
@@ -818,9 +558,7 @@ void ntt_free_tables(NttTables* t) {
   if (t->hi) (void)hipFree(t->hi);
   if (t->pass_tw) (void)hipFree(t->pass_tw);
   if (t->root64) (void)hipFree(t->root64);
-  if (t->lo29) (void)hipFree(t->lo29);
-  if (t->hi29) (void)hipFree(t->hi29);
-  t->lo = t->hi = t->pass_tw = t->root64 = t->lo29 = t->hi29 = nullptr;
+  t->lo = t->hi = t->pass_tw = t->root64 = nullptr;
 }
 
 hipError_t ntt_init_attributes() {
@@ -832,28 +570,24 @@ template <int M>
 static void launch_pass(const NttArgs& a, const NttIo& io, int B, int p, int first, uint64_t n_in, int L, int lrem,
                         int dist, const NttConst29& k29, hipStream_t st) {
   const uint64_t N = 1ull << L;
-  const uint64_t waves = N / ((1ull << M) * WaveDif<M>::CPW);
+  const uint64_t waves = N / ((1ull << M) * WaveDif29<M>::CPW);
   const unsigned blocks = (unsigned)((waves + NTT_WAVES - 1) / NTT_WAVES);
-  if (H2G_NTT29 && H2G_NTT_SPARSE && M == 3 && first && n_in <= (N >> 2)) {
+  if (M == 3 && first && n_in <= (N >> 2)) {
     const uint64_t S = N >> 3;
     hipLaunchKernelGGL(ntt_first_sparse29_kernel, dim3((unsigned)((S + NTT_THREADS - 1) / NTT_THREADS), (unsigned)B),
                        dim3(NTT_THREADS), 0, st, a.work, io, n_in, a.tab,
                        (const Fr*)(a.tab.pass_tw + a.tab.pass_off[p]), L, dist, k29);
     return;
   }
-  if (H2G_NTT29 && H2G_NTT_PIPE && !first) {  // two 4-wave blocks per CU over the whole batch, every wave several groups
+  if (!first) {  // two 4-wave blocks per CU over the whole batch, every wave several groups
     const uint64_t want = (uint64_t)ntt_cus() * 2 / (uint64_t)B;
     const unsigned pb = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(blocks, want));
     hipLaunchKernelGGL(ntt_pass29p_kernel<M>, dim3(pb, (unsigned)B), dim3(NTT_THREADS), 0, st, a.work, a.tab,
                        (const Fr*)(a.tab.pass_tw + a.tab.pass_off[p]), L, lrem, waves);
     return;
   }
-  if (H2G_NTT29)
-    hipLaunchKernelGGL(ntt_pass29_kernel<M>, dim3(blocks, (unsigned)B), dim3(NTT_THREADS), 0, st, a.work, io, first,
-                       n_in, a.tab, (const Fr*)(a.tab.pass_tw + a.tab.pass_off[p]), L, lrem, dist, k29);
-  else
-    hipLaunchKernelGGL(ntt_pass_kernel<M>, dim3(blocks, (unsigned)B), dim3(NTT_THREADS), 0, st, a.work, io, first,
-                       n_in, a.tab, (const Fr*)(a.tab.pass_tw + a.tab.pass_off[p]), L, lrem, dist, a.in_z1, a.in_z2);
+  hipLaunchKernelGGL(ntt_pass29_kernel<M>, dim3(blocks, (unsigned)B), dim3(NTT_THREADS), 0, st, a.work, io, first,
+                     n_in, a.tab, (const Fr*)(a.tab.pass_tw + a.tab.pass_off[p]), L, lrem, dist, k29);
 }
 
 hipError_t ntt_run(const NttArgs& a, hipStream_t st) {
@@ -890,7 +624,6 @@ hipError_t ntt_run(const NttArgs& a, hipStream_t st) {
     mul[r] = m;
     one = one && m == Fr::one();
   }
-  const int has_mul = !one;
   NttConst29 k29;  // the F29 passes' constants
   k29.z1 = storage_to_f29<FrParams>(a.in_z1);
   k29.z2 = storage_to_f29<FrParams>(a.in_z2);
@@ -913,25 +646,22 @@ hipError_t ntt_run(const NttArgs& a, hipStream_t st) {
     lrem -= lg[p];
   }
   {
-    const uint64_t waves = N / (64ull * WaveDif<6>::CPW);
+    const uint64_t waves = N / (64ull * WaveDif29<6>::CPW);
     const unsigned blocks = (unsigned)((waves + NTT_WAVES - 1) / NTT_WAVES);
     const dim3 g(blocks, (unsigned)B), b(NTT_THREADS);
     const bool tr = out_len < N;
-    if (H2G_NTT29 && tr && one)
+    if (tr && one)
       hipLaunchKernelGGL((ntt_last29_kernel<true, true>), g, b, 0, st, (const Fr*)a.work, io, out_len, a.tab, L, plan,
                          k29);
-    else if (H2G_NTT29 && tr)
+    else if (tr)
       hipLaunchKernelGGL((ntt_last29_kernel<true, false>), g, b, 0, st, (const Fr*)a.work, io, out_len, a.tab, L,
                          plan, k29);
-    else if (H2G_NTT29 && one)
+    else if (one)
       hipLaunchKernelGGL((ntt_last29_kernel<false, true>), g, b, 0, st, (const Fr*)a.work, io, out_len, a.tab, L,
                          plan, k29);
-    else if (H2G_NTT29)
+    else
       hipLaunchKernelGGL((ntt_last29_kernel<false, false>), g, b, 0, st, (const Fr*)a.work, io, out_len, a.tab, L,
                          plan, k29);
-    else
-      hipLaunchKernelGGL(ntt_last_kernel, dim3(blocks, (unsigned)B), dim3(NTT_THREADS), 0, st, (const Fr*)a.work,
-                         io, out_len, a.tab, L, plan, has_mul, mul[0], mul[1], mul[2]);
   }
   return hipGetLastError();
 }

@@ -87,11 +87,8 @@ struct InvBatch {
   Fr* pref[POLY_INV_MAX_BATCH];
 };
 static constexpr int INV_REG = 16;
-// the middle level's inversion: Bernstein-Yang divsteps (inv_by, uniform across the wave's
-// lanes) or the binary extended Euclid (inv, divergent); A/B builds -DH2G_INV_BY=0
-#ifndef H2G_INV_BY
-#define H2G_INV_BY 1
-#endif
+// the middle level's inversion is Bernstein-Yang divsteps (inv_by, uniform across the wave's
+// lanes); the binary extended Euclid (inv, divergent) was measured, rejected
 
 __global__ void __launch_bounds__(PT) inv_fwd_kernel(InvBatch bt, size_t n, size_t T) {
   const Fr* __restrict__ a = bt.a[blockIdx.y];
@@ -125,7 +122,7 @@ __global__ void __launch_bounds__(PT) inv_regs_kernel(InvBatch bt, size_t m) {
     pre[k] = acc;
     if (!v[k].is_zero()) acc = acc * v[k];
   }
-  Fr iv = H2G_INV_BY ? inv_by(acc) : inv(acc);
+  Fr iv = inv_by(acc);
 #pragma unroll
   for (int k = INV_REG - 1; k >= 0; k--) {
     const size_t i = t + k * T;

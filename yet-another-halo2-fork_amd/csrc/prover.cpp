@@ -262,7 +262,7 @@ struct ProvingKey {
   int2* d_seg_gate = nullptr;
   std::vector<int2> seg_lk_in, seg_lk_tab, seg_sh_in, seg_sh_sh;  // expression-list programs
   // lookup l's table expressions equal lookup lk_trep[l]'s (the first such; l itself when
-  // none): the proof sorts that table once (H2G_LK_SHARED_TABLES)
+  // none): the proof sorts that table once
   std::vector<int> lk_trep;
   Fr* consts = nullptr;
   int n_loads = 0;
@@ -475,10 +475,8 @@ uint64_t g_shard_seq = 0;
 h2g_spmd_transport g_spmd{nullptr, 1, 0, nullptr, nullptr};
 uint64_t g_spmd_seq = 0;
 // row pieces: the advice transforms run in the permutation stage when every transform of
-// the proof has a rank of its own (prove_impl); 0 keeps them in the advice stage (A/B)
-#ifndef H2G_DEFER_ADV_XFORM
-#define H2G_DEFER_ADV_XFORM 1
-#endif
+// the proof has a rank of its own (prove_impl; keeping them in the advice stage: measured,
+// rejected)
 // Single-GPU proofs: the columns' transforms (lagrange_to_coeff, the coset extension) on a
 // stream of their own (Device::xstream), joined before evaluate_h, their first reader.
 // On the prover's stream they held back every later stage's kernels -- the lookups'
@@ -489,17 +487,7 @@ uint64_t g_spmd_seq = 0;
 // lookups or shuffles: C3 (no lookups; its stages are MSM-bound, the chip already full)
 // measured 76.1-77.3 vs 73.1-73.8 ms with it.  The stream is created by the first proof
 // that uses it, after the MSM streams (the hardware-queue order matters, abi.cpp).  Stream
-// priorities (transforms low, or MSMs high) measured slower (profiles/r06/xs/).  0: on the
-// prover's stream.
-#ifndef H2G_XFORM_STREAM
-#define H2G_XFORM_STREAM 1
-#endif
-#ifndef H2G_LK_SHARED_TABLES  // A/B: 0 = every lookup sorts its own table column
-#define H2G_LK_SHARED_TABLES 1
-#endif
-#ifndef H2G_XS_ALL  // A/B: 1 = the transform stream for circuits without lookups too
-#define H2G_XS_ALL 0
-#endif
+// priorities (transforms low, or MSMs high) measured slower (profiles/r06/xs/).
 // overlapped exchanges (h2g_set_spmd_exchange_async); NULL post: exchanges complete on return
 h2g_spmd_exchange_post g_xpost = nullptr;
 h2g_spmd_exchange_wait g_xwait = nullptr;
@@ -747,10 +735,6 @@ int commit_collect_all(Device* d, MsmTicket* const* t, int nb, G1Affine* out) {
   xyzz_to_affine_batch(xz.data(), out, nb);
   return H2G_OK;
 }
-
-#ifndef H2G_LOOKUP_PREFIX  // A/B builds: 0 = the lookup commitments against the Lagrange basis itself
-#define H2G_LOOKUP_PREFIX 1
-#endif
 
 // Several commitments against one base set as batched MSMs (msm_run_fixed_batch): one
 // sort, accumulation and reduction serve a group, so the latency-bound reduction is paid
@@ -2338,12 +2322,11 @@ int prove_impl(Device* d, Params& prm, ProvingKey& pk, const ProveIn& in, std::v
   // which interpolate their sub-coset's h: C3 at 8 ranks puts its 6 column transforms on
   // ranks 2 .. 7 instead of stacking two roles on ranks 0 and 1)
   int tr_next = pieces ? E_sub : 0;
-  // the transform stream (H2G_XFORM_STREAM): xs_begin orders it after the prover stream's
+  // the transform stream: xs_begin orders it after the prover stream's
   // work so far (the inputs), xs_end marks its last transform, and the prover stream waits
   // for that mark before evaluate_h -- and at the end of the proof whatever its outcome
   // (XformJoin), so that the next proof's uploads never overtake a transform still reading
-  const bool xsplit =
-      H2G_XFORM_STREAM && g_spmd.world <= 1 && !spmd_subcosets() && (H2G_XS_ALL || pk.NL + pk.NS > 0);
+  const bool xsplit = g_spmd.world <= 1 && !spmd_subcosets() && pk.NL + pk.NS > 0;
   if (xsplit && !d->xstream) {  // after the MSM streams (h2g_init): the hardware-queue order, abi.cpp
     HIPCHK(hipStreamCreateWithFlags(&d->xstream, hipStreamNonBlocking));
     HIPCHK(hipEventCreateWithFlags(&d->xev_in, hipEventDisableTiming));
@@ -2404,7 +2387,7 @@ int prove_impl(Device* d, Params& prm, ProvingKey& pk, const ProveIn& in, std::v
   // ranks two transforms would share a rank in the permutation stage, measured slower:
   // profiles/r05/emulation/defer_adv/)
   const int n_xf = ncirc * (pk.A + pk.nsets + 3 * pk.NL + pk.NS);
-  const bool defer_adv = H2G_DEFER_ADV_XFORM && pieces && n_xf <= Wsp - E_sub;
+  const bool defer_adv = pieces && n_xf <= Wsp - E_sub;
   auto xform_later = [&](const std::vector<const Fr*>& lag, const std::vector<Fr*>& pol,
                          const std::vector<Fr*>& cst) {
     DeferredXform x{lag, pol, cst, std::vector<int>(lag.size())};
@@ -2523,14 +2506,9 @@ int prove_impl(Device* d, Params& prm, ProvingKey& pk, const ProveIn& in, std::v
   // advice handed over in host memory: the first column's upload has nothing to overlap
   // (its MSM needs the whole column), so the random polynomial's commitment goes first and
   // runs under that upload; device-resident advice keeps it behind the advice commitments
-  // (H2G_VAN_FIRST=1: first in both cases -- A/B builds)
-#ifndef H2G_VAN_FIRST
-#define H2G_VAN_FIRST 0
-#endif
-#ifndef H2G_VAN_POS
-#define H2G_VAN_POS 0
-#endif
-  const bool van_first = early_van && (!in.adv_dev || H2G_VAN_FIRST);
+  // and the advice transforms (first in both cases, or right behind the advice commitments
+  // and ahead of the transforms: measured, rejected)
+  const bool van_first = early_van && !in.adv_dev;
   for (int ph = 0; ph <= pk.max_phase; ph++) {
     if (ph == 0 && van_first) RCCHK(launch_van_early());
     std::vector<int> cols;
@@ -2634,9 +2612,6 @@ int prove_impl(Device* d, Params& prm, ProvingKey& pk, const ProveIn& in, std::v
       }
     }
     if (digest) RCCHK(spmd_witness_fold(pk, (int)(ncirc * cols.size()), st));
-    // H2G_VAN_POS 1: the random polynomial's commitment right behind the advice commitments,
-    // ahead of the advice transforms on the prover's stream (0: behind them)
-    if (ph == 0 && early_van && !van_first && H2G_VAN_POS == 1) RCCHK(launch_van_early());
     std::vector<int> adv_owner;
     std::vector<const Fr*> adv_lag;
     std::vector<Fr*> adv_poly, adv_cst;
@@ -2687,7 +2662,7 @@ int prove_impl(Device* d, Params& prm, ProvingKey& pk, const ProveIn& in, std::v
       for (int ci = 0; ci < ncirc; ci++)
         for (int c : cols) adv_shard[(size_t)ci * pk.A + c] = 1;
     }
-    if (ph == 0 && early_van && !van_first && H2G_VAN_POS == 0) RCCHK(launch_van_early());
+    if (ph == 0 && early_van && !van_first) RCCHK(launch_van_early());
     if (ph == 0) clk.mark("upload+instances");
     {  // circuit by circuit, column by column
       std::vector<MsmTicket*> tl;
@@ -2772,11 +2747,10 @@ int prove_impl(Device* d, Params& prm, ProvingKey& pk, const ProveIn& in, std::v
     // Lookups with identical table expressions (the same table, e.g. keccak's nibble-xor
     // columns for every lookup) share one sorted table: lookup j gathers it from lookup
     // tsrc[j]'s group.  Batch groups: the inputs [0, nown), then one per distinct table
-    // (H2G_LK_SHARED_TABLES; single-owner stages, and only while every lookup sorts by its
+    // (single-owner stages, and only while every lookup sorts by its
     // window -- a full sort writes its table group).  Otherwise two groups per lookup.
     std::vector<int> tsrc(NLT), gi0(NLT, -1), gi1(NLT, -1);
-    bool share = H2G_LK_SHARED_TABLES && !lk_wide && pk.lk_trep.size() == (size_t)pk.NL &&
-                 (int)pk.lk_hb.size() >= NLT;
+    bool share = !lk_wide && pk.lk_trep.size() == (size_t)pk.NL && (int)pk.lk_hb.size() >= NLT;
     for (int j = 0; j < NLT && share; j++)
       if (lq[j] >= 0 && pk.lk_hb[j] == 0) share = false;
     int ntab = 0;
@@ -3057,38 +3031,35 @@ int prove_impl(Device* d, Params& prm, ProvingKey& pk, const ProveIn& in, std::v
     for (int j = 0; j < NLT; j++) own2[2 * j] = own2[2 * j + 1] = lk_wide ? lk_owner[j] : g_spmd.rank;
     // A', S' against the prefix-summed Lagrange basis (params_prefix): the same commitments
     std::vector<const Fr*> com_cols = perm_cols;
-    int com_set = SRS_LAGRANGE;
-    if (H2G_LOOKUP_PREFIX) {
-      RCCHK(params_prefix(prm, st));
-      // scalars only for the columns this rank commits (all of them but in a wide stage,
-      // where a column belongs to its owner)
-      size_t owned = 0;
-      for (int i = 0; i < 2 * NLT; i++) owned += own2[i] == g_spmd.rank;
-      const size_t need = std::max<size_t>(owned, 1) * n;
-      if (need > pk.lk_diff_len) {
-        PALLOC(pk.pool, pk.lk_diff, need);
-        pk.lk_diff_len = need;
-      }
-      PrefixDiff pd{};
-      int m = 0;
-      size_t slot = 0;
-      for (int i = 0; i < 2 * NLT; i++) {
-        if (own2[i] != g_spmd.rank) {  // another rank's column (wide stage): not read here
-          com_cols[i] = perm_cols[i];
-          continue;
-        }
-        Fr* e = pk.lk_diff + (slot++) * n;
-        com_cols[i] = e;
-        pd.a[m] = perm_cols[i];
-        pd.e[m] = e;
-        if (++m == PREFIX_DIFF_MAX) {
-          HIPCHK(prefix_diff(pd, m, n, st));
-          m = 0;
-        }
-      }
-      if (m) HIPCHK(prefix_diff(pd, m, n, st));
-      com_set = SRS_LAGRANGE_PREFIX;
+    const int com_set = SRS_LAGRANGE_PREFIX;
+    RCCHK(params_prefix(prm, st));
+    // scalars only for the columns this rank commits (all of them but in a wide stage,
+    // where a column belongs to its owner)
+    size_t owned = 0;
+    for (int i = 0; i < 2 * NLT; i++) owned += own2[i] == g_spmd.rank;
+    const size_t need = std::max<size_t>(owned, 1) * n;
+    if (need > pk.lk_diff_len) {
+      PALLOC(pk.pool, pk.lk_diff, need);
+      pk.lk_diff_len = need;
     }
+    PrefixDiff pd{};
+    int m = 0;
+    size_t slot = 0;
+    for (int i = 0; i < 2 * NLT; i++) {
+      if (own2[i] != g_spmd.rank) {  // another rank's column (wide stage): not read here
+        com_cols[i] = perm_cols[i];
+        continue;
+      }
+      Fr* e = pk.lk_diff + (slot++) * n;
+      com_cols[i] = e;
+      pd.a[m] = perm_cols[i];
+      pd.e[m] = e;
+      if (++m == PREFIX_DIFF_MAX) {
+        HIPCHK(prefix_diff(pd, m, n, st));
+        m = 0;
+      }
+    }
+    if (m) HIPCHK(prefix_diff(pd, m, n, st));
     if (lk_wide) {
       RCCHK(commit_launch_owned(d, prm, com_cols.data(), own2.data(), 2 * NLT, n, com_set, st, tk.data()));
       RCCHK(xform(perm_cols, perm_polys, perm_cosets, &own2));
@@ -3242,49 +3213,8 @@ int prove_impl(Device* d, Params& prm, ProvingKey& pk, const ProveIn& in, std::v
     if (NST) dump("den0", W[0]->z_lag[0], n, st);
     HIPCHK(poly_batch_invert_multi(all_z_lag.data(), all_z.data(), NST, n, st));
     if (NST) dump("inv0", W[0]->z_lag[0], n, st);
-#ifndef H2G_PERM_MULTI  // 1: every set's numerators, then ONE batched scan of all sets (A/B)
-#define H2G_PERM_MULTI 0
-#endif
-    if (H2G_PERM_MULTI && NST > 1) {
-      // the sets' running products do not depend on each other (z_s = z_{s-1}'s last usable
-      // value x its own scan): one batched scan of every set's products into z's coefficient
-      // arrays (free until the iNTT), then each z assembled from the previous set's last value
-      // on the device -- the same values, the same RNG draws in the same order
-      for (int ci = 0; ci < ncirc; ci++) {
-        Fr deltaomega = Fr::one();
-        for (int s = 0; s < pk.nsets; s++) {
-          const int c0 = s * pk.chunk_len, c1 = std::min(c0 + pk.chunk_len, pk.P);
-          for (int c = c0; c < c1; c += PERM_MAXC) {
-            PermCols pc;
-            pc.m = std::min(PERM_MAXC, c1 - c);
-            for (int j = 0; j < pc.m; j++) {
-              pc.v[j] = col_vals(*W[ci], c + j);
-              pc.beta_delta[j] = deltaomega * beta;
-              deltaomega = deltaomega * fr_delta();
-            }
-            HIPCHK(perm_numerators(W[ci]->z_lag[s], n, pc, gamma, pk.om, st));
-          }
-        }
-      }
-      HIPCHK(poly_prefix_product_multi((const Fr* const*)all_z_lag.data(), all_z.data(), NST, n, pk.scr, pk.scr_len,
-                                       st));
-      for (int ci = 0; ci < ncirc; ci++) {
-        CircuitWs& w = *W[ci];
-        HIPCHK(hipMemcpyAsync(pk.last_z, pk.one, sizeof(Fr), hipMemcpyDeviceToDevice, st));  // z_0 starts at one
-        for (int s = 0; s < pk.nsets; s++) {
-          const size_t i = (size_t)ci * pk.nsets + s;
-          Fr* blind_rows = perm_blind.data() + i * bf;
-          for (int q = 0; q < bf; q++) blind_rows[q] = rng.random_fr();
-          (void)rng.random_fr();  // blind
-          HIPCHK(pk_upload(pk, pk.small, blind_rows, bf * sizeof(Fr), st));
-          HIPCHK(perm_z_assemble(w.z_lag[s], n, bf, all_z[i], pk.last_z, pk.small, st));
-          HIPCHK(hipMemcpyAsync(pk.last_z, w.z_lag[s] + (n - (size_t)(bf + 1)), sizeof(Fr), hipMemcpyDeviceToDevice,
-                                st));
-          if (!perm_batched) RCCHK(commit_launch(d, prm, w.z_lag[s], n, SRS_LAGRANGE, st, &perm_tk[i]));
-        }
-      }
-    }
-    for (int ci = 0; ci < ncirc && !(H2G_PERM_MULTI && NST > 1); ci++) {
+    // (every set's numerators, then one batched scan of all sets: measured, rejected)
+    for (int ci = 0; ci < ncirc; ci++) {
       CircuitWs& w = *W[ci];
       HIPCHK(hipMemcpyAsync(pk.last_z, pk.one, sizeof(Fr), hipMemcpyDeviceToDevice, st));  // z_0 starts at one
       Fr deltaomega = Fr::one();
@@ -4132,7 +4062,7 @@ int h2g_keygen(uint64_t params, const h2g_circuit* circuit, uint64_t* pk_out) {
   pk->params = params;
   int rc = keygen_impl(d, *it->second, circuit, *pk);
   // the lookup commitments' basis (params_prefix) now, not inside the first proof
-  if (!rc && circuit->num_lookups > 0 && H2G_LOOKUP_PREFIX) rc = params_prefix(*it->second, d->stream);
+  if (!rc && circuit->num_lookups > 0) rc = params_prefix(*it->second, d->stream);
   if (rc) {
     domain_release(&pk->dom);
     return rc;

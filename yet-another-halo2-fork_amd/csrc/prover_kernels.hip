@@ -131,89 +131,13 @@ hipError_t chacha_random_poly(Fr* out, size_t n, const uint32_t* d_seeds, const 
 // slot-major [slot][lane] 32-byte elements (gate_prog.h: EH_T, EH_MAX_SLOTS, run_prog).
 int evaluate_h_max_slots() { return EH_MAX_SLOTS; }
 
-__global__ void __launch_bounds__(EH_T) evaluate_h_kernel(EvalHArgs a) {
-  extern __shared__ uint4 eh_lds[];
-  Fr* sl = reinterpret_cast<Fr*>(eh_lds);
-  const int lane = threadIdx.x;
-  const uint64_t emask = a.ext - 1;
-  const uint64_t rend = a.rows ? a.row0 + a.rows : a.ext;
-  for (uint64_t idx = a.row0 + blockIdx.x * (uint64_t)EH_T + lane; idx < rend; idx += (uint64_t)gridDim.x * EH_T) {
-    Fr acc = run_prog(a.prog, a.gates, a.consts, a.query_col, a.query_rot, idx, a.rot_scale, emask, a.y, sl, lane,
-                      a.acc_in ? ldf(a.acc_in + idx) : Fr::zero());
-    const Fr l0 = ldf(a.l0 + idx);
-    const Fr ll = ldf(a.l_last + idx);
-    const Fr la = ldf(a.l_active + idx);
-    const uint64_t r_next = (idx + a.rot_scale) & emask;
-    if (a.nsets > 0) {
-      const uint64_t r_last = (idx + (uint64_t)((int64_t)a.last_rot * (int64_t)a.rot_scale)) & emask;
-      // l_0(X) * (1 - z_0(X))
-      acc = acc * a.y + (Fr::one() - ldf(a.z[0] + idx)) * l0;
-      // l_last(X) * (z_l(X)^2 - z_l(X))
-      {
-        const Fr zl = ldf(a.z[a.nsets - 1] + idx);
-        acc = acc * a.y + (zl * zl - zl) * ll;
-      }
-      // l_0(X) * (z_i(X) - z_{i-1}(omega^(last) X))
-      for (int s = 1; s < a.nsets; s++) acc = acc * a.y + (ldf(a.z[s] + idx) - ldf(a.z[s - 1] + r_last)) * l0;
-      // l_active(X) * (z_i(omega X) prod(p + beta sigma + gamma) - z_i(X) prod(p + delta^j beta X + gamma))
-      Fr cur = a.delta_start * pw(a.ext_omega, idx);
-      for (int s = 0; s < a.nsets; s++) {
-        const int c0 = s * a.chunk_len;
-        const int c1 = c0 + a.chunk_len < a.P ? c0 + a.chunk_len : a.P;
-        Fr left = ldf(a.z[s] + r_next);
-        Fr right = ldf(a.z[s] + idx);
-        for (int c = c0; c < c1; c++) {
-          const Fr v = ldf(a.perm_v[c] + idx);
-          left = left * (v + a.beta * ldf(a.sigma[c] + idx) + a.gamma);
-          right = right * (v + cur + a.gamma);
-          cur = cur * a.delta;
-        }
-        acc = acc * a.y + (left - right) * la;
-      }
-    }
-    if (a.nlookups + a.nshuffles > 0) {
-      const uint64_t r_prev = (idx - a.rot_scale) & emask;
-      for (int l = 0; l < a.nlookups; l++) {  // evaluation.rs:486-558
-        const EvalLookup lk = a.lookups[l];
-        const Fr ci = run_prog(a.prog, lk.in, a.consts, a.query_col, a.query_rot, idx, a.rot_scale, emask, a.theta,
-                               sl, lane);
-        const Fr ct = run_prog(a.prog, lk.tab, a.consts, a.query_col, a.query_rot, idx, a.rot_scale, emask, a.theta,
-                               sl, lane);
-        const Fr table_value = (ci + a.beta) * (ct + a.gamma);
-        const Fr z = ldf(lk.z + idx), ap = ldf(lk.ap + idx), sp = ldf(lk.sp + idx);
-        const Fr ams = ap - sp;
-        acc = acc * a.y + (Fr::one() - z) * l0;
-        acc = acc * a.y + (z * z - z) * ll;
-        acc = acc * a.y + (ldf(lk.z + r_next) * (ap + a.beta) * (sp + a.gamma) - z * table_value) * la;
-        acc = acc * a.y + ams * l0;
-        acc = acc * a.y + ams * (ap - ldf(lk.ap + r_prev)) * la;
-      }
-      for (int s = 0; s < a.nshuffles; s++) {  // evaluation.rs:561-620
-        const EvalShuffle sh = a.shuffles[s];
-        const Fr ci = run_prog(a.prog, sh.in, a.consts, a.query_col, a.query_rot, idx, a.rot_scale, emask, a.theta,
-                               sl, lane) + a.gamma;
-        const Fr cs = run_prog(a.prog, sh.sh, a.consts, a.query_col, a.query_rot, idx, a.rot_scale, emask, a.theta,
-                               sl, lane) + a.gamma;
-        const Fr z = ldf(sh.z + idx);
-        acc = acc * a.y + (Fr::one() - z) * l0;
-        acc = acc * a.y + (z * z - z) * ll;
-        acc = acc * a.y + la * (ldf(sh.z + r_next) * cs - z * ci);
-      }
-    }
-    stf(a.out + idx, a.divide ? acc * ldf(a.t_evals + (idx & a.t_mask)) : acc);
-  }
-}
-
-// ---- evaluate_h in F29 (f29.h), H2G_EVALH29 ---------------------------------------------
+// ---- evaluate_h in F29 (f29.h) -----------------------------------------------------------
 // Loads enter as to29 (the element, value < 32 M; a shift, no product), products are
 // f29.h's carry-free REDC, every sum and difference is normalised and reduced (reduce29,
 // < 1.001 M), so no value exceeds 64 M before a reduction and every product input is a
 // load / constant (< 32 M), a product (< 7 M) or a reduced sum: the columns stay far below
 // 2^64.  The row's result leaves with one product against the storage integer of t(X)^-1
 // (REDC(acc 2^261 e * t 2^256) = the storage form of acc * t, no conversion product).
-#ifndef H2G_EVALH29  // A/B builds: 0 = the 8 x 32-bit kernel above
-#define H2G_EVALH29 1
-#endif
 struct EvalH29Scalars {
   F29 theta, beta, gamma, y, delta_start, delta, one;
 };
@@ -366,21 +290,16 @@ hipError_t evaluate_h(const EvalHArgs& a, hipStream_t st) {
   if (a.n_slots > EH_MAX_SLOTS) return hipErrorInvalidValue;
   size_t blocks = ((a.rows ? a.rows : a.ext) + EH_T - 1) / EH_T;
   if (blocks > 256 * 32) blocks = 256 * 32;
-  if (H2G_EVALH29) {
-    const size_t lds = (size_t)(a.n_slots > 0 ? a.n_slots : 1) * EH_T * 9 * 4;
-    EvalH29Scalars k;
-    k.theta = storage_to_f29<FrParams>(a.theta);
-    k.beta = storage_to_f29<FrParams>(a.beta);
-    k.gamma = storage_to_f29<FrParams>(a.gamma);
-    k.y = storage_to_f29<FrParams>(a.y);
-    k.delta_start = storage_to_f29<FrParams>(a.delta_start);
-    k.delta = storage_to_f29<FrParams>(a.delta);
-    k.one = one29v<FrParams>();
-    hipLaunchKernelGGL(evaluate_h29_kernel, dim3((unsigned)blocks), dim3(EH_T), lds, st, a, k);
-  } else {
-    const size_t lds = (size_t)(a.n_slots > 0 ? a.n_slots : 1) * EH_T * sizeof(Fr);
-    hipLaunchKernelGGL(evaluate_h_kernel, dim3((unsigned)blocks), dim3(EH_T), lds, st, a);
-  }
+  const size_t lds = (size_t)(a.n_slots > 0 ? a.n_slots : 1) * EH_T * 9 * 4;
+  EvalH29Scalars k;
+  k.theta = storage_to_f29<FrParams>(a.theta);
+  k.beta = storage_to_f29<FrParams>(a.beta);
+  k.gamma = storage_to_f29<FrParams>(a.gamma);
+  k.y = storage_to_f29<FrParams>(a.y);
+  k.delta_start = storage_to_f29<FrParams>(a.delta_start);
+  k.delta = storage_to_f29<FrParams>(a.delta);
+  k.one = one29v<FrParams>();
+  hipLaunchKernelGGL(evaluate_h29_kernel, dim3((unsigned)blocks), dim3(EH_T), lds, st, a, k);
   return hipGetLastError();
 }
 
@@ -719,13 +638,9 @@ __device__ void block_suffix_affine(Fr val, Fr w, Fr* shv, Fr* shw, Fr* out_val,
 }
 
 // ------------------------------------------------------------------ polynomial evaluation
-// H2G_HORNER29 = 1: the Horner chains of eval_level1 and kate_phase1/3 in F29 (f29.h): the
-// recurrence is linear in the coefficients, so they enter as raw storage integers, the
-// point as an F29 element, and the accumulator is reduced only where it is stored.
-// 0: the 8 x 32-bit Montgomery chains (A/B builds).
-#ifndef H2G_HORNER29
-#define H2G_HORNER29 1
-#endif
+// The Horner chains of eval_level1 and kate_phase1/3 run in F29 (f29.h): the recurrence is
+// linear in the coefficients, so they enter as raw storage integers, the point as an F29
+// element, and the accumulator is reduced only where it is stored.
 __device__ __forceinline__ Fr f29_to_storage(const F29& v) {  // v < 2^260 -> [0, M)
   return pack29<FrParams>(sub_m_if_ge29<FrParams>(reduce29<FrParams>(norm29(v))));
 }
@@ -755,7 +670,7 @@ __global__ void __launch_bounds__(EV_T) eval_level1(const EvalReq* __restrict__ 
   // (Four independent Horner chains per thread measured slower: 1.22 vs 0.97 ms for C3
   // k = 22's batch -- the unrolled loads and accumulators halve the waves per SIMD.)
   __shared__ Fr pw[EV_L + 1];
-  __shared__ F29 x29;  // pw[EV_L] as an F29 element (H2G_HORNER29)
+  __shared__ F29 x29;  // pw[EV_L] as an F29 element
   const int t = threadIdx.x;
   if (t == 0) {
     Fr step = rq.x;
@@ -763,30 +678,19 @@ __global__ void __launch_bounds__(EV_T) eval_level1(const EvalReq* __restrict__ 
       pw[l] = step;
       step = step * step;
     }
-    if (H2G_HORNER29) x29 = storage_to_f29<FrParams>(pw[EV_L]);
+    x29 = storage_to_f29<FrParams>(pw[EV_L]);
   }
   __syncthreads();
   const uint64_t lo = base + (uint64_t)t;
-  Fr acc;
-  if constexpr (H2G_HORNER29) {
-    // F29 Horner (f29.h): storage integers enter raw, x^EV_T as an F29 element; the
-    // accumulator stays unreduced (< 6.4 M, tools/f29_bounds.py) and is reduced once
-    const F29 X = x29;
-    F29 a29{};
-    for (int i = EV_S - 1; i >= 0; i--) {
-      const uint64_t j = lo + (uint64_t)i * EV_T;
-      a29 = add29(mul29<FrParams>(a29, X), j < rq.len ? raw29(ldf(rq.poly + j)) : F29{});
-    }
-    acc = f29_to_storage(a29);
-  } else {
-    const Fr X = pw[EV_L];
-    acc = Fr::zero();
-    for (int i = EV_S - 1; i >= 0; i--) {
-      const uint64_t j = lo + (uint64_t)i * EV_T;
-      acc = acc * X + (j < rq.len ? ldf(rq.poly + j) : Fr::zero());
-    }
+  // F29 Horner (f29.h): storage integers enter raw, x^EV_T as an F29 element; the
+  // accumulator stays unreduced (< 6.4 M, tools/f29_bounds.py) and is reduced once
+  const F29 X = x29;
+  F29 a29{};
+  for (int i = EV_S - 1; i >= 0; i--) {
+    const uint64_t j = lo + (uint64_t)i * EV_T;
+    a29 = add29(mul29<FrParams>(a29, X), j < rq.len ? raw29(ldf(rq.poly + j)) : F29{});
   }
-  sh[t] = acc;
+  sh[t] = f29_to_storage(a29);
   __syncthreads();
 #pragma unroll
   for (int l = 0; l < EV_L; l++) {
@@ -860,17 +764,13 @@ struct KatePow {
 
 // Thread t's segment is KD_S consecutive coefficients, so a direct load by lane strides
 // KD_S x 32 B between lanes (a wave touches 64 lines per load and uses 32 B of each).  The
-// staged form (H2G_KATE_LDS) moves each segment's next KD_SUB coefficients for the whole
+// staged form moves each segment's next KD_SUB coefficients for the whole
 // block through LDS: every run of KD_SUB x 32 B = 128 B is loaded by 8 lanes with 16-B
 // loads (whole lines), each thread then reads its own run from LDS -- rows padded to
 // 144 B so the 16 lanes of a ds_read_b128 hit distinct banks.  Phase 3 stages its stored
-// quotients (and, accumulating, the old ones) the same way.  Phase 3 only by default
-// (H2G_KATE_LDS 1; 2 stages phase 1 too): at 2^22 phase 3 96 vs 135 us (136 vs 152 us
-// accumulating); the read-only phase 1 was faster unstaged, 76 vs 85 us
-// (profiles/r06/kate/).
-#ifndef H2G_KATE_LDS
-#define H2G_KATE_LDS 1
-#endif
+// quotients (and, accumulating, the old ones) the same way.  Phase 3 only: at 2^22
+// phase 3 96 vs 135 us unstaged (136 vs 152 us accumulating); staging the read-only
+// phase 1 too was measured, rejected: 85 vs 76 us unstaged (profiles/r06/kate/).
 #ifndef H2G_KD_SUB
 #define H2G_KD_SUB 4
 #endif
@@ -923,35 +823,13 @@ __global__ void __launch_bounds__(KD_T) kate_phase1(const Fr* __restrict__ a1, u
   __shared__ Fr sh[KD_T];
   const int t = threadIdx.x;
   const uint64_t lo = blockIdx.x * (uint64_t)(KD_T * KD_S) + (uint64_t)t * KD_S;
-  Fr acc;
-  if constexpr (H2G_HORNER29 && H2G_KATE_LDS >= 2) {  // measured slower for phase 1 (85 vs 76 us at 2^22)
-    __shared__ KateStage stg;
-    const uint64_t tile0 = blockIdx.x * (uint64_t)(KD_T * KD_S);
-    F29 a29{};
-    for (int c = KD_S / KD_SUB - 1; c >= 0; c--) {
-      __syncthreads();  // the previous run's reads are done
-      kate_stage_load<KD_S>(stg, a1, tile0, M, c);
-      __syncthreads();
+  F29 a29{};
 #pragma unroll
-      for (int i = KD_SUB - 1; i >= 0; i--) a29 = add29(mul29<FrParams>(a29, b29), raw29(kate_stage_get(stg, t, i)));
-    }
-    acc = f29_to_storage(a29);
-  } else if constexpr (H2G_HORNER29) {
-    F29 a29{};
-#pragma unroll
-    for (int i = KD_S - 1; i >= 0; i--) {
-      const uint64_t j = lo + i;
-      a29 = add29(mul29<FrParams>(a29, b29), j < M ? raw29(ldf(a1 + j)) : F29{});
-    }
-    acc = f29_to_storage(a29);
-  } else {
-    acc = Fr::zero();
-#pragma unroll
-    for (int i = KD_S - 1; i >= 0; i--) {
-      const uint64_t j = lo + i;
-      acc = acc * b + (j < M ? ldf(a1 + j) : Fr::zero());
-    }
+  for (int i = KD_S - 1; i >= 0; i--) {
+    const uint64_t j = lo + i;
+    a29 = add29(mul29<FrParams>(a29, b29), j < M ? raw29(ldf(a1 + j)) : F29{});
   }
+  const Fr acc = f29_to_storage(a29);
   stf(thr_val + blockIdx.x * (uint64_t)KD_T + t, acc);
   // sum_t acc_t b^(KD_S t): tree with the level weights
   sh[t] = acc;
@@ -1006,54 +884,31 @@ __global__ void __launch_bounds__(KD_T) kate_phase3(const Fr* __restrict__ a1, u
     if (t + s < KD_T) x = x + pw.p[l] * sh[t + s];
     __syncthreads();
   }
-  const uint64_t lo = blockIdx.x * (uint64_t)(KD_T * KD_S) + (uint64_t)t * KD_S;
-  if constexpr (H2G_HORNER29 && H2G_KATE_LDS) {
-    // staged: run c's coefficients in, its quotients out (and the old ones in, ACC) through
-    // LDS, every global access whole lines; the carried value stays unreduced (< 2.1 M)
-    // (a thread reads and writes only its own row: without ACC the quotients overwrite the
-    // coefficients they come from; with it the old quotients have a buffer of their own)
-    __shared__ KateStage stg;
-    KateStage* out = &stg;
-    if constexpr (ACC) {
-      __shared__ KateStage old;
-      out = &old;
-    }
-    const uint64_t tile0 = blockIdx.x * (uint64_t)(KD_T * KD_S);
-    F29 cur = raw29(x);
-    for (int c = KD_S / KD_SUB - 1; c >= 0; c--) {
-      __syncthreads();  // the previous run's reads and its coalesced stores are done
-      kate_stage_load<KD_S>(stg, a1, tile0, M, c);
-      if (ACC) kate_stage_load<KD_S>(*out, q, tile0, M, c);
-      __syncthreads();
+  // staged: run c's coefficients in, its quotients out (and the old ones in, ACC) through
+  // LDS, every global access whole lines; the carried value stays unreduced (< 2.1 M) and
+  // each stored quotient is reduced
+  // (a thread reads and writes only its own row: without ACC the quotients overwrite the
+  // coefficients they come from; with it the old quotients have a buffer of their own)
+  __shared__ KateStage stg;
+  KateStage* out = &stg;
+  if constexpr (ACC) {
+    __shared__ KateStage old;
+    out = &old;
+  }
+  const uint64_t tile0 = blockIdx.x * (uint64_t)(KD_T * KD_S);
+  F29 cur = raw29(x);
+  for (int c = KD_S / KD_SUB - 1; c >= 0; c--) {
+    __syncthreads();  // the previous run's reads and its coalesced stores are done
+    kate_stage_load<KD_S>(stg, a1, tile0, M, c);
+    if (ACC) kate_stage_load<KD_S>(*out, q, tile0, M, c);
+    __syncthreads();
 #pragma unroll
-      for (int i = KD_SUB - 1; i >= 0; i--) {
-        cur = add29(raw29(kate_stage_get(stg, t, i)), mul29<FrParams>(cur, b29));
-        kate_stage_put(*out, t, i, f29_to_storage(ACC ? add29(raw29(kate_stage_get(*out, t, i)), cur) : cur));
-      }
-      __syncthreads();
-      kate_stage_store<KD_S>(*out, q, tile0, M, c);
+    for (int i = KD_SUB - 1; i >= 0; i--) {
+      cur = add29(raw29(kate_stage_get(stg, t, i)), mul29<FrParams>(cur, b29));
+      kate_stage_put(*out, t, i, f29_to_storage(ACC ? add29(raw29(kate_stage_get(*out, t, i)), cur) : cur));
     }
-    return;
-  }
-  if constexpr (H2G_HORNER29) {
-    // the carried value stays unreduced (< 2.1 M); each stored quotient is reduced
-    F29 cur = raw29(x);
-    for (int i = KD_S - 1; i >= 0; i--) {
-      const uint64_t j = lo + i;
-      if (j < M) {
-        cur = add29(raw29(ldf(a1 + j)), mul29<FrParams>(cur, b29));
-        stf(q + j, f29_to_storage(ACC ? add29(raw29(ldf(q + j)), cur) : cur));
-      }
-    }
-    return;
-  }
-  Fr cur = x;
-  for (int i = KD_S - 1; i >= 0; i--) {
-    const uint64_t j = lo + i;
-    if (j < M) {
-      cur = ldf(a1 + j) + b * cur;
-      stf(q + j, ACC ? ldf(q + j) + cur : cur);
-    }
+    __syncthreads();
+    kate_stage_store<KD_S>(*out, q, tile0, M, c);
   }
 }
 
@@ -1092,7 +947,7 @@ hipError_t kate_division(const Fr* a, uint64_t len, const Fr& b, Fr* q, Fr* scra
   }
   Fr* tile = scratch;
   Fr* thr = scratch + nt + 1;
-  const F29 b29 = storage_to_f29<FrParams>(b);  // b as an F29 element (H2G_HORNER29)
+  const F29 b29 = storage_to_f29<FrParams>(b);  // b as an F29 element
   switch (S) {
     case 8: kate_launch<8>(a, M, b, b29, pw, tile, thr, q, nt, st, accumulate); break;
     case 16: kate_launch<16>(a, M, b, b29, pw, tile, thr, q, nt, st, accumulate); break;
@@ -1103,22 +958,10 @@ hipError_t kate_division(const Fr* a, uint64_t len, const Fr& b, Fr* q, Fr* scra
 }
 
 // ------------------------------------------------------------------ linear combinations
-__global__ void __launch_bounds__(KT) lincomb_kernel(Fr* __restrict__ out, uint64_t n, LinTerms t, int acc_in) {
-  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    Fr acc = acc_in ? ldf(out + i) : Fr::zero();
-    for (int k = 0; k < t.k; k++)
-      if (i < t.len[k]) acc = acc + t.coef[k] * ldf(t.p[k] + i);
-    stf(out + i, acc);
-  }
-}
-
-// The same in F29 (f29.h): the map is linear, so the storage integers of the columns enter
-// raw, the coefficients as proper F29 elements, and two terms share one reduction
-// (mul29x2); every pair's result is < 1.02 M, their sum (with the accumulated value) is
-// brought to [0, M) by reduce29 and one subtraction.  H2G_LINCOMB29 = 0: the kernel above.
-#ifndef H2G_LINCOMB29
-#define H2G_LINCOMB29 1
-#endif
+// out (+)= sum_k coef_k p_k in F29 (f29.h): the map is linear, so the storage integers of
+// the columns enter raw, the coefficients as proper F29 elements, and two terms share one
+// reduction (mul29x2); every pair's result is < 1.02 M, their sum (with the accumulated
+// value) is brought to [0, M) by reduce29 and one subtraction.
 struct LinTerms29 {
   const Fr* p[LIN_MAXT];
   uint64_t len[LIN_MAXT];
@@ -1144,18 +987,14 @@ __global__ void __launch_bounds__(KT) lincomb29_kernel(Fr* __restrict__ out, uin
 
 hipError_t lincomb(Fr* out, uint64_t n, const LinTerms& t, bool accumulate, hipStream_t st) {
   if (n == 0) return hipSuccess;
-  if (H2G_LINCOMB29) {
-    LinTerms29 t29;
-    t29.k = t.k;
-    for (int k = 0; k < t.k; k++) {
-      t29.p[k] = t.p[k];
-      t29.len[k] = t.len[k];
-      t29.coef[k] = storage_to_f29<FrParams>(t.coef[k]);
-    }
-    hipLaunchKernelGGL(lincomb29_kernel, dim3(grid_1d(n)), dim3(KT), 0, st, out, n, t29, accumulate ? 1 : 0);
-    return hipGetLastError();
+  LinTerms29 t29;
+  t29.k = t.k;
+  for (int k = 0; k < t.k; k++) {
+    t29.p[k] = t.p[k];
+    t29.len[k] = t.len[k];
+    t29.coef[k] = storage_to_f29<FrParams>(t.coef[k]);
   }
-  hipLaunchKernelGGL(lincomb_kernel, dim3(grid_1d(n)), dim3(KT), 0, st, out, n, t, accumulate ? 1 : 0);
+  hipLaunchKernelGGL(lincomb29_kernel, dim3(grid_1d(n)), dim3(KT), 0, st, out, n, t29, accumulate ? 1 : 0);
   return hipGetLastError();
 }
 
