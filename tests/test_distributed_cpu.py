@@ -126,7 +126,7 @@ def test_slab_protocol_gloo(world):
 # ---------------------------------------------------------------- SPMD: every rank proves
 def _spmd_worker(rank, world, port, jobs, bases, q):
     """h2g_dist.SpmdGather over gloo with the prover's slab rule (h2g_dist.slab of the
-    params' P) and its rank-order sum (csrc/prover.cpp commit_collect), the oracle MSM as
+    params' P) and its rank-order sum (csrc/commit.cpp commit_collect), the oracle MSM as
     each rank's slab engine (no GPU here): every rank must hold the unsharded MSM"""
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)

@@ -1,4 +1,4 @@
-"""A rank's slab of the params and the prefix-summed Lagrange basis (csrc/prover.cpp
+"""A rank's slab of the params and the prefix-summed Lagrange basis (csrc/params.cpp
 params_prefix): the windows of the basis P_i = L_0 + ... + L_i that the lookup
 commitments use are built for the slab on the first set-2 MSM inside it -- what a shard
 mode peer's serve loop runs (h2g_comm_serve) -- and never as the full-size table there

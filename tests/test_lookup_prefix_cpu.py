@@ -1,4 +1,4 @@
-"""The identity behind the lookup commitments' prefix basis (prover.cpp params_prefix,
+"""The identity behind the lookup commitments' prefix basis (params.cpp params_prefix,
 SRS_LAGRANGE_PREFIX): with P_i = L_0 + ... + L_i,
 
     sum_i a_i L_i  ==  sum_i (a_i - a_{i+1}) P_i      (a_n = 0),

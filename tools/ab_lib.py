@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """A/B of a library built from a previous revision of one source: compile `src_file` (a
 copy of e.g. csrc/prover.cpp from an older commit) with the current build's flags and link
-it with the other objects of the current build into lib_ab/libh2g_<tag>.so.
+it with the current build's other objects (those of build_lib.sources(), so an object a
+removed source left in build/ is not linked) into lib_ab/libh2g_<tag>.so.
 usage: python tools/ab_lib.py TAG SRC_FILE OBJ_TO_REPLACE   (e.g. prev /tmp/prover.cpp prover.cpp)"""
-import glob
 import os
 import subprocess
 import sys
@@ -15,7 +15,7 @@ import build_lib as B  # noqa: E402
 tag, src, replaced = sys.argv[1:4]
 out_dir = os.path.join(B.PKG, "lib_ab")
 os.makedirs(out_dir, exist_ok=True)
-objs = [o for o in glob.glob(os.path.join(B.BUILD, "*.o")) if not o.endswith(replaced + ".o")]
+objs = [os.path.join(B.BUILD, os.path.basename(s) + ".o") for s in B.sources() if os.path.basename(s) != replaced]
 obj = os.path.join(out_dir, f"{tag}.o")
 subprocess.run([B.HIPCC] + B.CFLAGS + ["-I", B.CSRC, "-x", "hip", "-c", src, "-o", obj], check=True)
 lib = os.path.join(out_dir, f"libh2g_{tag}.so")

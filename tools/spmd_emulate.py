@@ -38,7 +38,7 @@ def _fq_mont_limbs(v):
     return [(m >> (64 * i)) & (2**64 - 1) for i in range(4)]
 
 
-COMMIT_TAG = 0x54494d4d4f433248  # prover.cpp kSpmdCommitTag
+COMMIT_TAG = 0x54494d4d4f433248  # commit.cpp kSpmdCommitTag
 G1_GEN_MONT = np.array(_fq_mont_limbs(1) + _fq_mont_limbs(2), dtype=np.uint64)  # (1, 2), Montgomery form
 
 

@@ -77,7 +77,7 @@ struct Comm {
 };
 Comm* g_comm = nullptr;
 
-size_t slab_lo(uint64_t P, uint64_t n, int world, int r) {  // prover.cpp shard_lo
+size_t slab_lo(uint64_t P, uint64_t n, int world, int r) {  // commit.cpp shard_lo
   const uint64_t b = (uint64_t)((unsigned __int128)P * (unsigned)r / (unsigned)world);
   return b < n ? b : n;
 }

@@ -8,7 +8,7 @@
 //                     (count x 32 B, from a device staging copy of the prover's scalars)
 //   rx (r -> rank 0): int64[9] = affine partial (8 limbs) + identity flag
 // SPMD mode all-gathers H2G_SPMD_WORDS words per rank instead (partial, flag, digest).
-// Definitions in comm.cpp; the peers' serve loop (h2g_comm_serve) lives in prover.cpp next
+// Definitions in comm.cpp; the peers' serve loop (h2g_comm_serve) lives in spmd.cpp next
 // to the params it computes against.
 #pragma once
 #include <hip/hip_runtime.h>

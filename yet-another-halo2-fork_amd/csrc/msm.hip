@@ -1057,7 +1057,7 @@ hipError_t msm_fixed_base_build(const G1Affine* d_bases, size_t n, int c, MsmFix
   return hipGetLastError();
 }
 
-// prefix sums of points (the lookup commitments' prefix basis, prover.cpp): chunk scans of
+// prefix sums of points (the lookup commitments' prefix basis, params.cpp): chunk scans of
 // PFX_C points per thread at two levels, a serial scan of the top level (<= 1024 sums at
 // 2^22 points), and the offsets added back
 static constexpr uint32_t PFX_C = 64;

@@ -1,5 +1,5 @@
 // runtime.h -- host-side device runtime shared by the C ABI (abi.cpp) and the
-// prover orchestrator (prover.cpp): per-device state (stream, MSM workspace,
+// prover orchestrator (prover.cpp and the files around prover_state.h): per-device state (stream, MSM workspace,
 // grow-only scratch buffers, NTT twiddle tables), evaluation domains, error
 // reporting.  Definitions live in abi.cpp.
 #pragma once

@@ -21,7 +21,7 @@ OP_STOP, OP_MSM = 0, 1
 
 def slab(n, world, r, P=None, weights=None):
     """[lo, hi) of rank r's points in an MSM of length n: the slab of the params' P = 2^k
-    points, clipped to n (the C prover's shard_lo, csrc/prover.cpp); with SPMD weights
+    points, clipped to n (the C prover's shard_lo, csrc/commit.cpp); with SPMD weights
     (h2g.spmd_set_weights) [P S_r / S, P S_{r+1} / S)"""
     P = n if P is None else P
     if weights:
@@ -42,7 +42,7 @@ def auto_owner_weight(world, extended_k, k):
     return 0.5 if world <= 2 * E else 0.1
 
 
-COLSHARD_MIN_WORLD = 4  # prover.cpp kColshardMinWorld
+COLSHARD_MIN_WORLD = 4  # prover_state.h kColshardMinWorld
 
 
 def row_pieces_active(world, extended_k, k, column_owners=True, multiopen="shplonk"):
