@@ -4,7 +4,8 @@
 The subtraction constants are read from the sources, not restated: every
 `sub29<P, K, OFF>` the kernels instantiate (f29.h's XYZZ formulas, msm.hip's quad
 variants, ntt.hip's stage subtraction and sparse first pass, prover_kernels.hip's
-evaluate_h helpers) and is_zero29's early-out threshold are parsed
+evaluate_h helpers), every fused `subn29<P, K>` of the accumulation's hot-loop form
+(`source_fused_constants`) and is_zero29's early-out threshold are parsed
 (`source_constants`) and the model below runs on exactly those numbers.  `EXPECTED` is
 the snapshot this model was last reviewed against; tests/test_f29_bounds_cpu.py fails
 when the sources drift from it (any edit of a K, OFF or the threshold) and when the
@@ -41,6 +42,7 @@ SOURCES = ("f29.h", "msm.hip", "ntt.hip", "prover_kernels.hip")
 # source order; K as written, e.g. ntt.hip's stage expression)
 EXPECTED = {
     "f29.h:xyzz29_madd": [("64", "29"), ("64", "29"), ("32", "31"), ("64", "29"), ("16", "29")],
+    "f29.h:xyzz29_madd_acc": [("64", "29"), ("16", "29")],
     "f29.h:xyzz29_dbl": [("4", "31"), ("4", "29"), ("2", "29")],
     "f29.h:xyzz29_add": [("2", "29"), ("2", "29"), ("4", "31"), ("4", "29"), ("2", "29")],
     "msm.hip:xyzz29_dbl_q4": [("4", "31"), ("4", "29"), ("2", "29")],
@@ -52,6 +54,13 @@ EXPECTED = {
     "is_zero29": 1024,
 }
 
+# the fused subtract-and-normalise sites, subn29<P, K> ("file:function": [K, ...] in source
+# order): kept apart from EXPECTED, whose entries are sub29 sites only
+EXPECTED_FUSED = {
+    "f29.h:xyzz29_madd_acc": ["64", "64", "32"],
+}
+
+_SUBN = re.compile(r"\bsubn29<\s*\w+\s*,\s*(\d+)\s*>")
 _SUB = re.compile(r"\bsub29<\s*\w+\s*,\s*(\([^()]*\)|[^,<>]+?)\s*,\s*(\d+)\s*>")
 _FUNC = re.compile(r"([A-Za-z_]\w*)\s*\(")
 _NOT_FUNC = {"__launch_bounds__", "if", "for", "while", "switch", "return", "sizeof", "static_assert", "defined"}
@@ -98,6 +107,25 @@ def source_constants(texts=None):
     return found
 
 
+def source_fused_constants(texts=None):
+    """{"file:function": [K, ...]} for every subn29<P, K> outside comments (f29.h)"""
+    text = (texts or {}).get("f29.h")
+    if text is None:
+        with open(os.path.join(CSRC, "f29.h")) as f:
+            text = f.read()
+    code = re.sub(r"//[^\n]*", lambda m: " " * len(m.group(0)), text)
+    funcs = _enclosing_functions(code)
+    found = {}
+    for m in _SUBN.finditer(code):
+        name = None
+        for start, nm in funcs:
+            if start > m.start():
+                break
+            name = nm
+        found.setdefault(f"f29.h:{name}", []).append(m.group(1))
+    return found
+
+
 def k_of(expr, s=None):
     """the integer K of a parsed constant (ntt.hip's stage form "(4u << S)" at stage s)"""
     e = expr.replace("u", "")
@@ -122,6 +150,15 @@ def sub_ok(b, k, off, b_limb=N29, m=M):
     unit = 1 << (off - 29)
     assert b_limb <= 1 << off, ("sub29 low limbs of b above 2^OFF", k, off)
     assert top(k * m) - unit >= top(b), ("sub29 K too small", k, off, LG(b), LG(k * m))
+
+
+def subn_ok(a, b, k, a_limb=N29, b_limb=N29, m=M):
+    """subn29<K>(a, b) = a - b + k M by a signed carry chain over normalised limbs of k M:
+    k M >= b as integers (the top limb, which takes what is left, stays >= 0 and below
+    2^32), and every limb's signed sum a_i - b_i + (k M)_i + carry fits 32 bits"""
+    assert k * m >= b, ("subn29 K too small", k, LG(b), LG(k * m))
+    assert top(a + k * m) < 1 << 32, ("subn29 top limb", LG(a + k * m))
+    assert a_limb + N29 + 8 < 1 << 31 and b_limb + 8 < 1 << 31, ("subn29 limb sums", a_limb, b_limb)
 
 
 def sub_limb(off, a_limb=N29):
@@ -169,11 +206,43 @@ def madd(st, xq, yq, ks, thr):
     return (X3, Y3, ZZ3, ZZZ3), inter
 
 
-def madd_fixpoint(st, ks, thr):
+def madd_acc(st, xq, yq, ks, ns, thr):
+    """xyzz29_madd_acc (f29.h), the accumulation's hot-loop form, on bounds: the three
+    normalised differences are subn29<K> (ns: their K in source order), the two operands
+    of the closing double product sub29 (ks); the chained products have mul29's columns"""
+    (k3, o3), (k4, o4) = [(k_of(k), int(o)) for k, o in ks]
+    n0, n1, n2 = [int(k) for k in ns]
+    X, Y, ZZ, ZZZ = st
+    U2, S2 = mul(xq, ZZ), mul(yq, ZZZ)
+    subn_ok(U2, X, n0)
+    subn_ok(S2, Y, n1)
+    P, Rr = U2 + n0 * M, S2 + n1 * M
+    iszero_ok(P, thr)
+    iszero_ok(Rr, thr)
+    PP, R2 = mul(P, P), mul(Rr, Rr)
+    PPP, Q = mul(P, PP), mul(X, PP)
+    subn_ok(R2, PPP + 2 * Q, n2, b_limb=3 * (N29 - 1))  # add29(add29(PPP, Q), Q): unnormalised
+    X3 = R2 + n2 * M
+    sub_ok(X3, k3, o3)
+    D = Q + k3 * M
+    sub_ok(PPP, k4, o4)
+    E = k4 * M
+    column_ok(N29, N29)
+    column_ok(N29, sub_limb(o3), N29, sub_limb(o4, a_limb=0))
+    Y3 = (Rr * D + Y * E) // R + M + 1
+    ZZ3, ZZZ3 = mul(ZZ, PP), mul(ZZZ, PPP)
+    inter = dict(U2=U2, S2=S2, P=P, R=Rr, PP=PP, PPP=PPP, Q=Q, R2=R2, X3=X3, D=D, E=E, Y3=Y3)
+    for k, v in inter.items():
+        assert v < 1 << 261, (k, LG(v))
+    return (X3, Y3, ZZ3, ZZZ3), inter
+
+
+def madd_fixpoint(st, ks, thr, ns=None):
+    """ns: the subn29 constants of xyzz29_madd_acc (then ks are its two sub29 sites)"""
     xq = yq = 32 * M
     worst = 0
     for _ in range(60):
-        nxt, inter = madd(st, xq, yq, ks, thr)
+        nxt, inter = madd(st, xq, yq, ks, thr) if ns is None else madd_acc(st, xq, yq, ks, ns, thr)
         worst = max(worst, *nxt, *inter.values())
         st = tuple(max(a, b) for a, b in zip(st, nxt))  # bounds only grow
     return st, worst
@@ -240,10 +309,11 @@ def ntt_pass(stages, b0, kexpr, off):
     return B * MR // R + MR + 1
 
 
-def check(consts=None, verbose=False):
-    """run the whole model on `consts` (default: parsed from the sources); AssertionError
-    names the first violated bound"""
+def check(consts=None, verbose=False, fused=None):
+    """run the whole model on `consts` and `fused` (default: parsed from the sources);
+    AssertionError names the first violated bound"""
     c = consts if consts is not None else source_constants()
+    fu = fused if fused is not None else source_fused_constants()
     say = print if verbose else (lambda *a, **k: None)
     thr = c["is_zero29"]
     madd_ks = c["f29.h:xyzz29_madd"]
@@ -252,7 +322,13 @@ def check(consts=None, verbose=False):
     d = mul(32 * M, M)
     fd, w2 = madd_fixpoint((d, d, d, d), madd_ks, thr)
     say(f"doubling path: fixpoint log2 X Y ZZ ZZZ = {[round(LG(v), 3) for v in fd]}, largest intermediate 2^{LG(w2):.3f}")
-    acc_max = max(fx + fd)
+    # the hot-loop form: the same class (the stored accumulators feed the same fixup)
+    acc_ks, acc_ns = c["f29.h:xyzz29_madd_acc"], fu["f29.h:xyzz29_madd_acc"]
+    ax, w3 = madd_fixpoint((32 * M, 32 * M, M, M), acc_ks, thr, acc_ns)
+    ad, w4 = madd_fixpoint((d, d, d, d), acc_ks, thr, acc_ns)
+    say(f"hot-loop form: fixpoint log2 X Y ZZ ZZZ = {[round(LG(v), 3) for v in ax]} (fresh), "
+        f"{[round(LG(v), 3) for v in ad]} (doubling path), largest intermediate 2^{LG(max(w3, w4)):.3f}")
+    acc_max = max(fx + fd + ax + ad)
     assert acc_max < 1 << 260
     assert reduce29(1 << 260) < 1.001 * M
     bworst = 0
@@ -348,6 +424,7 @@ def check(consts=None, verbose=False):
     assert MR + (qh + 2) * (1 << 232) < 2 * MR
     say(f"Horner chains: accumulator < {h / MR:.2f} M, stored sums < {stored / MR:.2f} M, reduced below 2 M")
     return {"madd_fixpoint": tuple(max(a, b) for a, b in zip(fx, fd)), "madd_intermediate": max(w1, w2),
+            "madd_acc_fixpoint": tuple(max(a, b) for a, b in zip(ax, ad)), "madd_acc_intermediate": max(w3, w4),
             "backend_out": bworst}
 
 
@@ -358,7 +435,10 @@ def main():
         for k in sorted(set(c) | set(EXPECTED)):
             if c.get(k) != EXPECTED.get(k):
                 print(f"  {k}: sources {c.get(k)} snapshot {EXPECTED.get(k)}")
-    check(c, verbose=True)
+    fu = source_fused_constants()
+    if fu != EXPECTED_FUSED:
+        print(f"WARNING: the sources' subn29 constants {fu} differ from EXPECTED_FUSED {EXPECTED_FUSED}")
+    check(c, verbose=True, fused=fu)
     print("ok")
 
 

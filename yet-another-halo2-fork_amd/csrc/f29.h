@@ -402,6 +402,174 @@ H2G_HD G1xyzz29 xyzz29_madd(const G1xyzz29& p, const F29& qx, const F29& qy, boo
 }
 
 
+// ---- the accumulation's hot-loop forms (msm_acc.hip) ----------------------------------
+// msm_acc_kernel is bound by instruction issue alone (DESIGN, "The accumulation's issue
+// cost"), so these forms exist to execute fewer instructions; they compute the same integers
+// as the forms above, limb for limb.
+//
+// Carry-chained products.  The compiler reassociates a column's sum however the source
+// orders it: every column starts from 0 and the previous column's shifted carry is joined
+// with a separate 64-bit add (mul29's two-chain source and a single chain compile to the
+// same code).  H2G_PIN64 after every multiply-add (an empty asm on the accumulator) hides
+// each partial sum's origin from the reassociation, so the carry stays the column's first
+// addend: the join becomes the v_mad_u64_u32's own third operand.  Pinning less does not
+// hold: the unpinned rest of a column forms its own chain from 0 and is joined again.  The
+// product is then one dependent chain of mads; four waves per SIMD cover its latency.  The
+// pin is not free: the compiler puts one s_nop behind each (the wait state a reader of an
+// asm-defined register is owed), about half of what the joins were worth (DESIGN).
+// Same contracts as mul29 / sqr29 / mul29x2.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define H2G_PIN64(x) asm("" : "+v"(x))
+#else
+#define H2G_PIN64(x) ((void)0)
+#endif
+#define H2G_MAC(acc, x, y)          \
+  do {                              \
+    acc += (uint64_t)(x) * (y);     \
+    H2G_PIN64(acc);                 \
+  } while (0)
+template <class P>
+H2G_HD F29 mul29_acc(const F29& a, const F29& b) {
+  uint32_t m[9];
+  F29 r;
+  uint64_t acc = 0;
+#pragma unroll
+  for (int k = 0; k < 17; k++) {
+    const int i0 = k > 8 ? k - 8 : 0, i1 = k > 8 ? 8 : k;
+    H2G_MAC(acc, a.l[i0], b.l[k - i0]);
+#pragma unroll
+    for (int i = i0 + 1; i <= i1; i++) H2G_MAC(acc, a.l[i], b.l[k - i]);
+    if (k < 9) {
+#pragma unroll
+      for (int i = 0; i < k; i++) H2G_MAC(acc, m[i], C29<P>::M[k - i]);
+      m[k] = ((uint32_t)acc * C29<P>::INV) & F29_MASK;
+      H2G_MAC(acc, m[k], C29<P>::M[0]);
+    } else {
+#pragma unroll
+      for (int i = k - 8; i < 9; i++) H2G_MAC(acc, m[i], C29<P>::M[k - i]);
+      r.l[k - 9] = (uint32_t)acc & F29_MASK;
+    }
+    acc >>= 29;
+  }
+  r.l[8] = (uint32_t)acc;
+  return r;
+}
+template <class P>
+H2G_HD F29 sqr29_acc(const F29& a) {
+  uint32_t m[9], d[9];
+#pragma unroll
+  for (int i = 0; i < 9; i++) d[i] = a.l[i] << 1;
+  F29 r;
+  uint64_t acc = 0;
+#pragma unroll
+  for (int k = 0; k < 17; k++) {
+    const int i0 = k > 8 ? k - 8 : 0;
+    if (2 * i0 < k) H2G_MAC(acc, d[i0], a.l[k - i0]);
+    else H2G_MAC(acc, a.l[k / 2], a.l[k / 2]);  // k = 0, 16: the square is the only term
+#pragma unroll
+    for (int i = i0 + 1; 2 * i < k; i++) H2G_MAC(acc, d[i], a.l[k - i]);
+    if ((k & 1) == 0 && 2 * i0 < k) H2G_MAC(acc, a.l[k / 2], a.l[k / 2]);
+    if (k < 9) {
+#pragma unroll
+      for (int i = 0; i < k; i++) H2G_MAC(acc, m[i], C29<P>::M[k - i]);
+      m[k] = ((uint32_t)acc * C29<P>::INV) & F29_MASK;
+      H2G_MAC(acc, m[k], C29<P>::M[0]);
+    } else {
+#pragma unroll
+      for (int i = k - 8; i < 9; i++) H2G_MAC(acc, m[i], C29<P>::M[k - i]);
+      r.l[k - 9] = (uint32_t)acc & F29_MASK;
+    }
+    acc >>= 29;
+  }
+  r.l[8] = (uint32_t)acc;
+  return r;
+}
+template <class P>
+H2G_HD F29 mul29x2_acc(const F29& a, const F29& b, const F29& c, const F29& d) {
+  uint32_t m[9];
+  F29 r;
+  uint64_t acc = 0;
+#pragma unroll
+  for (int k = 0; k < 17; k++) {
+    const int i0 = k > 8 ? k - 8 : 0, i1 = k > 8 ? 8 : k;
+    H2G_MAC(acc, a.l[i0], b.l[k - i0]);
+    H2G_MAC(acc, c.l[i0], d.l[k - i0]);
+#pragma unroll
+    for (int i = i0 + 1; i <= i1; i++) {
+      H2G_MAC(acc, a.l[i], b.l[k - i]);
+      H2G_MAC(acc, c.l[i], d.l[k - i]);
+    }
+    if (k < 9) {
+#pragma unroll
+      for (int i = 0; i < k; i++) H2G_MAC(acc, m[i], C29<P>::M[k - i]);
+      m[k] = ((uint32_t)acc * C29<P>::INV) & F29_MASK;
+      H2G_MAC(acc, m[k], C29<P>::M[0]);
+    } else {
+#pragma unroll
+      for (int i = k - 8; i < 9; i++) H2G_MAC(acc, m[i], C29<P>::M[k - i]);
+      r.l[k - 9] = (uint32_t)acc & F29_MASK;
+    }
+    acc >>= 29;
+  }
+  r.l[8] = (uint32_t)acc;
+  return r;
+}
+
+// a - b + K M, normalised, in one pass: a signed carry chain (subtract, add the constant's
+// limb and the carry, shift, mask: 4 ops per limb against 5 for norm29(sub29<..>(a, b))).
+// K M is taken in plain normalised limbs -- a limb may go negative, its borrow travels in
+// the carry -- so the only conditions are K M >= b as integers (then the top limb, which
+// takes what is left, is >= 0) and limbs small enough for 32-bit signed sums: a's below
+// 2^30, b's below 2^31 - 2^30.  The result is the same integer as the sub29 form's, hence
+// the same limbs.  (tools/f29_bounds.py reads K from every call, like sub29's.)
+template <class P, uint32_t K>
+struct KMN29 {
+  static constexpr Limbs9 n = kmul_norm<P>(K);
+  static constexpr uint32_t L[9] = {n.v[0], n.v[1], n.v[2], n.v[3], n.v[4], n.v[5], n.v[6], n.v[7], n.v[8]};
+};
+template <class P, uint32_t K>
+H2G_HD F29 subn29(const F29& a, const F29& b) {
+  F29 r;
+  int32_t c = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    const int32_t t = (int32_t)(a.l[i] - b.l[i]) + (int32_t)KMN29<P, K>::L[i] + c;
+    r.l[i] = (uint32_t)t & F29_MASK;
+    c = t >> 29;
+  }
+  r.l[8] = (a.l[8] - b.l[8]) + KMN29<P, K>::L[8] + (uint32_t)c;
+  return r;
+}
+
+// p += q inside a run of the accumulation: xyzz29_madd's arithmetic (the same values,
+// bit for bit) for a p that is not the identity -- the caller starts a run from its first
+// point and keeps "p is the identity" in a flag, so neither a 9-limb test of ZZ nor the
+// copy of q sits in the hot loop's path.  Straight-line on purpose: a branch around the
+// products makes the compiler keep the old and the new point in different registers and
+// copy 36 of them at every join.  Returns 0, or 1 when the sum is the identity (p == -q),
+// or 2 when p == q (the caller redoes the chunk with xyzz29_madd<true>, whose doubling
+// branch this form leaves out like xyzz29_madd<false>); p is meaningless after 1 or 2.
+H2G_HD int xyzz29_madd_acc(G1xyzz29& p, const F29& qx, const F29& qy) {
+  using P = FqParams;
+  const F29 U2 = mul29_acc<P>(qx, p.ZZ);
+  const F29 S2 = mul29_acc<P>(qy, p.ZZZ);
+  const F29 Pp = subn29<P, 64>(U2, p.X);
+  const F29 R = subn29<P, 64>(S2, p.Y);
+  int st = 0;
+  if (is_zero29<P>(Pp)) st = is_zero29<P>(R) ? 2 : 1;
+  // ZZ and ZZZ first: PP dies there and PPP lives on only as 16 M - PPP (register pressure)
+  const F29 PP = sqr29_acc<P>(Pp);
+  const F29 Q = mul29_acc<P>(p.X, PP);
+  const F29 PPP = mul29_acc<P>(Pp, PP);
+  p.ZZ = mul29_acc<P>(p.ZZ, PP);
+  p.ZZZ = mul29_acc<P>(p.ZZZ, PPP);
+  const F29 R2 = sqr29_acc<P>(R);
+  p.X = subn29<P, 32>(R2, add29(add29(PPP, Q), Q));  // R^2 - PPP - 2Q
+  p.Y = mul29x2_acc<P>(R, sub29<P, 64, 29>(Q, p.X), p.Y, sub29<P, 16, 29>(F29{}, PPP));  // R (Q - X3) - Y PPP
+  return st;
+}
+
+
 // ---- linear maps on storage-form data (the NTT): for a map that is linear over Fr, the
 // storage integers x (x = e 2^256 mod M) can be taken as F29 values directly -- read as F29
 // they stand for e 2^-5 -- and every constant (twiddle, coset power, scale) as a proper F29

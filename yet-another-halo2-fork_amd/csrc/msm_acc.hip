@@ -29,18 +29,16 @@ __device__ __forceinline__ G1Affine ld_aff(const G1Affine* p) {
 // The accumulator is F29 (f29.h) and is stored raw -- a run end is a handful of
 // stores, not a conversion: some lane of a wave ends a run on most steps, so anything
 // costlier there would be paid by the whole wave nearly every step.
-__device__ __forceinline__ void msm_emit(uint32_t key, const AccPoint& acc, bool first, bool from_prev, bool to_next,
-                                         uint32_t t, AccPoint* __restrict__ buckets, AccPoint* __restrict__ bnd) {
+// ident: the run's sum is the identity and acc's registers hold anything (the hot loop's flag)
+__device__ __forceinline__ void msm_emit(uint32_t key, const AccPoint& acc, bool ident, bool first, bool from_prev,
+                                         bool to_next, uint32_t t, AccPoint* __restrict__ buckets,
+                                         AccPoint* __restrict__ bnd) {
   AccPoint* dst = (!from_prev && !to_next) ? buckets + key : bnd + 2 * (size_t)t + (first ? 0 : 1);
-  st_acc(dst, acc);
+  if (ident) st_acc(dst, xyzz29_identity());
+  else st_acc(dst, acc);
 }
 
 __device__ __forceinline__ AccPoint acc_identity() { return xyzz29_identity(); }
-template <bool SAFE>
-__device__ __forceinline__ AccPoint acc_madd(const AccPoint& acc, const G1Affine& pt, bool* dbl) {
-  if (pt.is_identity()) return acc;
-  return xyzz29_madd<SAFE>(acc, to29(pt.x), to29(pt.y), dbl);
-}
 
 // one chunk [t L, t L + L) of the sorted values: the runs it holds to their buckets or to
 // its boundary slots.  SAFE = false: the mixed addition without its doubling branch (the
@@ -48,7 +46,12 @@ __device__ __forceinline__ AccPoint acc_madd(const AccPoint& acc, const G1Affine
 // SIMD -- measured, rejected); returns true when a run met p == q, and the chunk must be
 // redone with SAFE = true -- its writes go to the same places, every one of them rewritten.
 // The next entry's base point is loaded before the current mixed addition (software-
-// pipelined gather), so its latency hides behind ~3000 VALU ops.
+// pipelined gather), so its latency hides behind ~2300 VALU ops.
+// The hot form (SAFE = false) keeps "acc is the identity" in the flag `fresh`, not in
+// acc.ZZ: a run starts from its first point by plain selects (acc = (x, y, 1, 1) on the
+// lanes whose flag is set), and the straight-line xyzz29_madd_acc runs on the lanes that
+// are inside a run.  The flag is set again by p == -q in the middle of a
+// run (and by identity bases), so the point after it starts the run afresh.
 template <bool SAFE>
 __device__ __forceinline__ bool acc_chunk(uint32_t t, const G1Affine* __restrict__ bases,
                                           const uint32_t* __restrict__ vals, const uint32_t* __restrict__ koff,
@@ -67,7 +70,7 @@ __device__ __forceinline__ bool acc_chunk(uint32_t t, const G1Affine* __restrict
   }
   const bool prev_same = koff[key] < lo;
   uint32_t kend = koff[key + 1];
-  bool first = true, dbl = false;
+  bool first = true, dbl = false, fresh = true;
   AccPoint acc = acc_identity();
   uint32_t v = vals[lo];
   G1Affine pt = ld_aff(bases + (v & 0x7fffffffu));
@@ -75,7 +78,7 @@ __device__ __forceinline__ bool acc_chunk(uint32_t t, const G1Affine* __restrict
     const uint32_t v_next = vals[p + 1 < hi ? p + 1 : p];
     const G1Affine pt_next = ld_aff(bases + (v_next & 0x7fffffffu));
     if (p == kend) {  // the run of `key` ended at p: the next non-empty bucket starts here
-      msm_emit(key, acc, first, first && prev_same, false, t, buckets, bnd);
+      msm_emit(key, acc, !SAFE && fresh, first, first && prev_same, false, t, buckets, bnd);
       first = false;
       // the largest k with koff[k] <= p (koff[key + 1] == p): usually key + 1; empty
       // buckets in between (concentrated digits leave long empty ranges) are crossed by
@@ -94,21 +97,39 @@ __device__ __forceinline__ bool acc_chunk(uint32_t t, const G1Affine* __restrict
       }
       key = a;
       kend = koff[key + 1];
-      acc = acc_identity();
+      if constexpr (SAFE) acc = acc_identity();
+      fresh = true;
     }
     if (v >> 31) pt = affine_neg(pt);
-    acc = acc_madd<SAFE>(acc, pt, &dbl);
+    if constexpr (SAFE) {
+      if (!pt.is_identity()) acc = xyzz29_madd<true>(acc, to29(pt.x), to29(pt.y));
+    } else {
+      const bool skip = pt.is_identity(), start = fresh;
+      const F29 qx = to29(pt.x), qy = to29(pt.y);
+      if (!skip && start) {  // before the addition: qx, qy are dead once it has read them
+        acc.X = qx;
+        acc.Y = qy;
+        acc.ZZ = one29v<FqParams>();
+        acc.ZZZ = acc.ZZ;
+        fresh = false;
+      }
+      if (!skip && !start) {
+        const int st = xyzz29_madd_acc(acc, qx, qy);
+        fresh = st != 0;
+        dbl |= st == 2;
+      }
+    }
     v = v_next;
     pt = pt_next;
   }
-  msm_emit(key, acc, first, first && prev_same, kend > hi, t, buckets, bnd);
+  msm_emit(key, acc, !SAFE && fresh, first, first && prev_same, kend > hi, t, buckets, bnd);
   return dbl;
 }
 
 // the chunks whose runs met p == q (same point twice in a row of one bucket: repeated bases
 // of a generic MSM; never for distinct SRS points), recorded for the repair pass:
 // rep[0] = count, rep[1 ..] = chunk ids (up to MSM_REPAIR_CAP; beyond it every chunk is redone)
-__global__ void __launch_bounds__(MSM_THREADS)
+__global__ void __launch_bounds__(MSM_THREADS, 4)
 msm_acc_kernel(const G1Affine* __restrict__ bases, const uint32_t* __restrict__ vals,
                const uint32_t* __restrict__ koff, uint32_t nbt, const uint32_t* __restrict__ d_total,
                AccPoint* __restrict__ buckets, AccPoint* __restrict__ bnd, uint32_t* __restrict__ rep) {
