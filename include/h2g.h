@@ -85,6 +85,25 @@ int h2g_msm_dev_cfg(const void* d_coeffs, const void* d_bases, size_t n, int win
 int h2g_msm_dev_host(const void* d_coeffs, const void* d_bases, size_t n, int window_bits, uint64_t out_affine[8],
                      int* out_is_identity, void* stream);
 int h2g_descriptor_device_ptr(uint64_t handle, void** d_ptr, size_t* n);
+/* Segmented small MSM: nseg independent sums in one launch, one affine result each (a batch
+ * verifier's shape: two ~10^2-term sums per proof over bases the proofs share).  CSR over one
+ * base array: segment s is the terms j in [seg_off[s], seg_off[s + 1]),
+ *   out[s] = sum_j scalars[j] * bases[index ? index[j] : j].
+ * Exact for every input: empty segments (identity), zero scalars, identity bases, the same
+ * base twice, a base and its negation.  One workgroup per segment: meant for many short
+ * segments, correct for any length.
+ * _dev: asynchronous on `stream`; the offsets must not decrease and every index must be below
+ * nbases -- the caller's contract (an index >= nbases is skipped, never dereferenced; offsets
+ * past the scalar array are not detected).  The host entry point checks both (H2G_ERR_ARG),
+ * copies in and out and returns when the results are ready. */
+int h2g_msm_segmented_dev(const void* d_bases, size_t nbases,      /* G1Affine, identity = zeros */
+                          const void* d_scalars,                   /* seg_off[nseg] Fr (Montgomery) */
+                          const uint32_t* d_index,                 /* base index per term; NULL = 0..nnz-1 */
+                          const uint32_t* d_seg_off,               /* nseg + 1 offsets into scalars / index */
+                          size_t nseg, void* d_out_affine,         /* nseg x 8 u64, identity = zeros */
+                          void* stream);
+int h2g_msm_segmented(const uint64_t* bases, size_t nbases, const uint64_t* scalars, const uint32_t* index,
+                      const uint32_t* seg_off, size_t nseg, uint64_t* out_affine);
 
 /* ---- SRS generation on device: g_i = [s^i] G, i < n
  * (ParamsKZG::setup, halo2_backend/src/poly/kzg/commitment.rs:64-90). s in Montgomery form. */
@@ -394,6 +413,65 @@ typedef struct {
   uint32_t num_copies;
 } h2g_check_inputs;
 int h2g_check_witness(uint64_t pk, const h2g_check_inputs* in, h2g_check_failure* out, size_t cap, uint64_t* total);
+
+/* ---- verify_proof (halo2_backend/src/plonk/verifier.rs:58-512) with the KZG multi-open
+ * verifiers (poly/kzg/multiopen/{shplonk,gwc}/verifier.rs) and DualMSM::check
+ * (poly/kzg/msm.rs:188-206), for hosts without the Rust crate and for batches.
+ * VerifyingKey (plonk.rs:42-231): the constraint system plus the fixed and permutation
+ * commitments, host memory only.  The constraint system comes from `circuit` as for
+ * h2g_pk_read (circuit->fixed_values / ->copies unused).  h2g_vk_write's bytes are the leading
+ * bytes of h2g_pk_write's in the same format; out == NULL returns the length. */
+int h2g_vk_from_pk(uint64_t pk, uint64_t* vk);            /* computes the fixed/permutation commitments if the key has none yet */
+int h2g_vk_read(const h2g_circuit* circuit, const uint8_t* buf, size_t len, int format, uint64_t* vk);  /* VerifyingKey::read, plonk.rs:73-129 */
+int h2g_vk_write(uint64_t vk, int format, uint8_t* out, size_t cap, size_t* len);
+int h2g_vk_free(uint64_t vk);
+/* ParamsVerifierKZG: the three points a verifier needs (G1 generator g[0], g2, s_g2), no SRS on
+ * the device; the params need their G2 points (h2g_params_setup / _read / _set_g2) */
+typedef struct { uint64_t g1[8], g2[16], s_g2[16]; } h2g_verifier_params;
+int h2g_params_verifier(uint64_t params, h2g_verifier_params* out);
+typedef struct {
+  const uint8_t* proof; size_t proof_len;
+  uint32_t num_circuits;                 /* >= 1 */
+  const uint64_t* const* instance;       /* [num_circuits]: the columns' values concatenated, instance_lens[c][i] Fr each (no padding to n) */
+  const uint32_t* const* instance_lens;  /* [num_circuits][num_instance] */
+} h2g_verify_item;
+/* MALFORMED: what verify_proof answers with an Err before the pairing -- a proof of the wrong
+ * length (the key, the circuit count and the multi-open scheme fix it), a point encoding with
+ * x >= p or off the curve, the point at infinity, an evaluation >= r, an instance value >= r or
+ * more instance values than usable rows.  REJECTED: well formed, the pairing equation fails. */
+enum { H2G_VERIFY_OK = 1, H2G_VERIFY_REJECTED = 0, H2G_VERIFY_MALFORMED = -1 };
+/* SingleStrategy (kzg/strategy.rs:146-186): one proof, one pairing check.  multiopen and
+ * transcript take the codes of h2g_pk_set_multiopen / h2g_pk_set_transcript.  The points are
+ * decompressed and the DualMSM's two sums evaluated on the device (the path of
+ * h2g_verify_batch with one item and no random factor).  Returns H2G_OK with the answer in
+ * *verdict; an error code only for bad arguments, unknown handles or device errors. */
+int h2g_verify_proof(uint64_t vk, const h2g_verifier_params* vp, int multiopen, int transcript,
+                     const h2g_verify_item* item, int32_t* verdict);
+/* A batch: one verdict per proof, at about one pairing check for a batch without bad proofs.
+ * All point encodings of all proofs are decompressed in one launch, every proof's transcript
+ * and scalar assembly runs on the host, one segmented MSM gives each well-formed proof's
+ * (L_i, R_i), and e(sum r_i L_i, s_g2) = e(sum r_i R_i, g2) is decided for random nonzero r_i.
+ * This is AccumulatorStrategy's random linear combination (kzg/strategy.rs:126-137) with one
+ * difference: the reference answers for the whole batch, this call for each proof -- a failing
+ * set of more than one proof is halved and both halves are tested, a failing set of one is
+ * REJECTED, so f bad proofs among B cost at most 1 + 2 f ceil(log2 B) pairing checks, and a
+ * malformed proof costs none and does not touch the others.  An accepted set is sound up to
+ * probability ~ 1 / r over the choice of the r_i.
+ * rng: the source of the r_i (random_fr, or 64 bytes of fill_bytes per draw).  NULL draws them
+ * from the operating system's generator, never from a fixed seed: THE r_i MUST BE
+ * UNPREDICTABLE to whoever made the proofs -- with known r_i two invalid proofs can be built
+ * whose errors cancel in the combination, and both would be accepted.  A seeded rng is for
+ * tests.
+ * verdicts[count]; stats (may be NULL): [0] pairing checks, [1] MSM terms of the per-proof
+ * sums, [2] points decompressed, [3] host milliseconds (transcripts, scalar assembly and
+ * pairings; rounded).  Shard and SPMD transports take no part. */
+int h2g_verify_batch(uint64_t vk, const h2g_verifier_params* vp, int multiopen, int transcript,
+                     const h2g_verify_item* items, size_t count, const h2g_rng* rng,
+                     int32_t* verdicts, uint64_t stats[4]);
+/* wall milliseconds of the last h2g_verify_proof / h2g_verify_batch: [0] host (transcripts,
+ * scalar assembly, the r_i), [1] decompression (upload, kernel, copy back), [2] the segmented
+ * MSMs (uploads, kernels, results), [3] pairing checks */
+int h2g_verify_stages(double ms[4]);
 
 /* wall milliseconds of the stages of the last h2g_create_proof (names: h2g_prover_stage_name).
  * Stages end when their work is queued, unless h2g_prover_stage_sync(1) is set: then each

@@ -47,7 +47,7 @@ void add_query(std::vector<Query>& l, const Query& q) {
   if (std::find(l.begin(), l.end(), q) == l.end()) l.push_back(q);
 }
 
-void collect(const CircuitView& v, int i, ProvingKey& pk) {  // keygen.rs:217-249, lhs before rhs
+void collect(const CircuitView& v, int i, CsHost& pk) {  // keygen.rs:217-249, lhs before rhs
   const int32_t* nd = v.node(i);
   switch (nd[0]) {
     case OP_CONST:
@@ -323,26 +323,23 @@ int build_pow_table(Pool& pool, const Fr& w, int L, PowTable* t, hipStream_t st)
   return H2G_OK;
 }
 
-int keygen_impl(Device* d, Params& prm, const h2g_circuit* c, ProvingKey& pk, const PkImage* img = nullptr) {
-  hipStream_t st = d->stream;
+// the constraint system's shape and a host copy of its expressions
+int cs_host_build(const h2g_circuit* c, CsHost* out) {
+  CsHost& pk = *out;
+  pk = CsHost{};
   std::string why;
-  if (c->k != prm.k) return fail(H2G_ERR_ARG, "keygen: circuit k != params k");
   if (c->num_gates && (!c->gate_roots || !c->nodes)) return fail(H2G_ERR_ARG, "keygen: null gates");
   if (!check_nodes(c, &why)) return fail(H2G_ERR_ARG, "keygen: bad expression graph: " + why);
-  if (!img && c->num_fixed && !c->fixed_values) return fail(H2G_ERR_ARG, "keygen: null fixed values");
   if (!c->transcript_repr) return fail(H2G_ERR_ARG, "keygen: null transcript_repr");
+  if (c->k > FR_S) return fail(H2G_ERR_ARG, "keygen: k too large");
   const CircuitView cv{c};
-  pk.device = d->id;
+  const size_t n = (size_t)1 << c->k;
   pk.k = c->k;
-  pk.n = (size_t)1 << c->k;
   pk.A = (int)c->num_advice;
   pk.F = (int)c->num_fixed;
   pk.I = (int)c->num_instance;
   pk.P = (int)c->num_perm_columns;
   pk.transcript_repr = fr_from_limbs(c->transcript_repr);
-  pk.unblinded.assign(pk.A, 0);
-  if (c->unblinded)
-    for (int i = 0; i < pk.A; i++) pk.unblinded[i] = c->unblinded[i];
   pk.adv_phase.assign(pk.A, 0);
   if (c->advice_phase)
     for (int i = 0; i < pk.A; i++) pk.adv_phase[i] = c->advice_phase[i];
@@ -353,7 +350,7 @@ int keygen_impl(Device* d, Params& prm, const h2g_circuit* c, ProvingKey& pk, co
   for (int i = 0; i < pk.A; i++) pk.max_phase = std::max(pk.max_phase, (int)pk.adv_phase[i]);
   for (uint8_t ph : pk.ch_phase)
     if ((int)ph > pk.max_phase) return fail(H2G_ERR_ARG, "keygen: challenge phase after the last advice phase");
-  pk.num_consts = (int)c->num_constants;
+  if (pk.P && !c->perm_columns) return fail(H2G_ERR_ARG, "keygen: null permutation columns");
   for (int i = 0; i < pk.P; i++) {
     const int t = c->perm_columns[2 * i], ix = c->perm_columns[2 * i + 1];
     const int lim = t == COL_ADVICE ? pk.A : t == COL_FIXED ? pk.F : t == COL_INSTANCE ? pk.I : 0;
@@ -404,9 +401,62 @@ int keygen_impl(Device* d, Params& prm, const h2g_circuit* c, ProvingKey& pk, co
     maxq = *std::max_element(cnt.begin(), cnt.end());
   }
   pk.bf = std::max(3, maxq) + 2;
-  if ((int64_t)pk.n < pk.bf + 3) return fail(H2G_ERR_ARG, "keygen: not enough rows available");
+  if ((int64_t)n < pk.bf + 3) return fail(H2G_ERR_ARG, "keygen: not enough rows available");
   pk.chunk_len = pk.degree - 2;
   pk.nsets = (pk.P + pk.chunk_len - 1) / pk.chunk_len;
+  // the host copy of the expression graph
+  if (c->num_nodes) pk.nodes.assign(c->nodes, c->nodes + 4 * (size_t)c->num_nodes);
+  if (c->num_constants && !c->constants) return fail(H2G_ERR_ARG, "keygen: null constants");
+  pk.constants.resize(c->num_constants);
+  for (uint32_t i = 0; i < c->num_constants; i++) pk.constants[i] = fr_from_limbs(c->constants + 4 * i);
+  if (c->num_gates) pk.gate_roots.assign(c->gate_roots, c->gate_roots + c->num_gates);
+  for (const auto& a : lks) {
+    pk.lk_in.emplace_back(a.in, a.in + a.m);
+    pk.lk_tab.emplace_back(a.other, a.other + a.m);
+  }
+  for (const auto& a : shs) {
+    pk.sh_in.emplace_back(a.in, a.in + a.m);
+    pk.sh_sh.emplace_back(a.other, a.other + a.m);
+  }
+  return H2G_OK;
+}
+
+int keygen_impl(Device* d, Params& prm, const h2g_circuit* c, ProvingKey& pk, const PkImage* img = nullptr) {
+  hipStream_t st = d->stream;
+  if (c->k != prm.k) return fail(H2G_ERR_ARG, "keygen: circuit k != params k");
+  RCCHK(cs_host_build(c, &pk.cs));
+  if (!img && c->num_fixed && !c->fixed_values) return fail(H2G_ERR_ARG, "keygen: null fixed values");
+  const CircuitView cv{c};
+  const std::vector<ArgRoots> lks = arg_roots(c->num_lookups, c->lookup_sizes, c->lookup_roots);
+  const std::vector<ArgRoots> shs = arg_roots(c->num_shuffles, c->shuffle_sizes, c->shuffle_roots);
+  {
+    const CsHost& cs = pk.cs;
+    pk.device = d->id;
+    pk.k = cs.k;
+    pk.n = (size_t)1 << cs.k;
+    pk.A = cs.A;
+    pk.F = cs.F;
+    pk.I = cs.I;
+    pk.P = cs.P;
+    pk.NL = cs.NL;
+    pk.NS = cs.NS;
+    pk.transcript_repr = cs.transcript_repr;
+    pk.unblinded.assign(pk.A, 0);
+    if (c->unblinded)
+      for (int i = 0; i < pk.A; i++) pk.unblinded[i] = c->unblinded[i];
+    pk.adv_phase = cs.adv_phase;
+    pk.ch_phase = cs.ch_phase;
+    pk.max_phase = cs.max_phase;
+    pk.num_consts = (int)c->num_constants;
+    pk.perm_cols = cs.perm_cols;
+    pk.degree = cs.degree;
+    pk.adv_q = cs.adv_q;
+    pk.fix_q = cs.fix_q;
+    pk.ins_q = cs.ins_q;
+    pk.bf = cs.bf;
+    pk.chunk_len = cs.chunk_len;
+    pk.nsets = cs.nsets;
+  }
   RCCHK(domain_init(&pk.dom, (uint32_t)pk.degree, pk.k));
   pk.ext = (size_t)1 << pk.dom.ek;
   pk.rot_scale = 1ull << (pk.dom.ek - pk.k);

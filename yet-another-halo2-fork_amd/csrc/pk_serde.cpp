@@ -193,9 +193,82 @@ int count_bad_fr(const std::vector<std::pair<const Fr*, size_t>>& arrays, hipStr
   (void)hipFree(bad);
   return H2G_OK;
 }
+
+// VerifyingKey::write (plonk.rs:73-86): version, k, the fixed column count, the fixed
+// commitments, then permutation::VerifyingKey::write -- the head of a written ProvingKey and
+// all of a written VerifyingKey (h2g_vk_write)
+void vk_write_prefix(ByteWriter& w, uint32_t k, const std::vector<G1Affine>& fixed, const std::vector<G1Affine>& perm) {
+  w.u8(PK_VERSION);
+  w.u8((uint8_t)k);
+  w.u32le((uint32_t)fixed.size());
+  for (const auto& c : fixed) w.g1(c);
+  for (const auto& c : perm) w.g1(c);
+}
+// VerifyingKey::read (plonk.rs:88-129) up to the commitments; the constraint system is the caller's
+int vk_read_prefix(ByteReader& r, int format, const h2g_circuit* circuit, const char* who, std::vector<G1Affine>* vf,
+                   std::vector<G1Affine>* vp) {
+  const std::string w = who;
+  const bool proc = format == SERDE_PROCESSED;
+  if (r.u8() != PK_VERSION) return fail(H2G_ERR_ARG, w + ": unexpected version byte");
+  const uint32_t k = r.u8();
+  if (!r.ok || k != circuit->k) return fail(H2G_ERR_ARG, w + ": k does not match");
+  const uint32_t F = r.u32le();
+  if (!r.ok || F != circuit->num_fixed) return fail(H2G_ERR_ARG, w + ": fixed column count does not match");
+  vf->assign(F, G1Affine{Fq::zero(), Fq::zero()});
+  vp->assign(circuit->num_perm_columns, G1Affine{Fq::zero(), Fq::zero()});
+  bool enc_ok = true;
+  for (auto* v : {vf, vp})
+    for (auto& c : *v) {
+      if (proc) {
+        if (const uint8_t* b = r.take(32)) enc_ok = g1_decompress_host(b, &c) && enc_ok;
+      } else if (const uint8_t* b = r.take(sizeof(G1Affine))) {
+        std::memcpy(&c, b, sizeof(G1Affine));
+      }
+    }
+  if (!r.ok) return fail(H2G_ERR_ARG, w + ": truncated verifying key");
+  if (!enc_ok) return fail(H2G_ERR_ARG, w + ": invalid point encoding in the verifying key");
+  if (format == SERDE_RAW) {
+    for (const auto& c : *vf)
+      if (!g1_valid_host(c)) return fail(H2G_ERR_ARG, w + ": invalid fixed commitment");
+    for (const auto& c : *vp)
+      if (!g1_valid_host(c)) return fail(H2G_ERR_ARG, w + ": invalid permutation commitment");
+  }
+  return H2G_OK;
+}
 }  // namespace
 
 extern "C" {
+
+/* VerifyingKey::write / read (plonk.rs:73-129): the prefix of h2g_pk_write's bytes */
+int h2g_vk_write(uint64_t vk, int format, uint8_t* out, size_t cap, size_t* len) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  auto it = g_vks.find(vk);
+  if (it == g_vks.end()) return fail(H2G_ERR_HANDLE, "unknown verifying key");
+  if (!len) return fail(H2G_ERR_ARG, "vk_write: null length");
+  if (format != SERDE_RAW && format != SERDE_RAW_UNCHECKED && format != SERDE_PROCESSED)
+    return fail(H2G_ERR_ARG, "vk_write: unknown SerdeFormat");
+  ByteWriter w{out, out ? cap : 0, nullptr};
+  w.proc = format == SERDE_PROCESSED;
+  vk_write_prefix(w, it->second->cs.k, it->second->fixed, it->second->perm);
+  *len = w.len;
+  if (out && w.len > cap) return fail(H2G_ERR_ARG, "vk_write: buffer too small");
+  return H2G_OK;
+}
+
+int h2g_vk_read(const h2g_circuit* circuit, const uint8_t* buf, size_t len, int format, uint64_t* vk) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  if (!circuit || !buf || !vk) return fail(H2G_ERR_ARG, "vk_read: null argument");
+  if (format != SERDE_RAW && format != SERDE_RAW_UNCHECKED && format != SERDE_PROCESSED)
+    return fail(H2G_ERR_ARG, "vk_read: unknown SerdeFormat");
+  auto key = std::make_unique<VerifyingKey>();
+  RCCHK(cs_host_build(circuit, &key->cs));
+  ByteReader r{buf, len};
+  RCCHK(vk_read_prefix(r, format, circuit, "vk_read", &key->fixed, &key->perm));
+  if (r.pos != len) return fail(H2G_ERR_ARG, "vk_read: trailing bytes");
+  *vk = g_next_handle++;
+  g_vks[*vk] = std::move(key);
+  return H2G_OK;
+}
 
 /* ParamsKZG::write_custom (kzg/commitment.rs:166-181): k (u32 LE), g, g_lagrange, g2, s_g2 */
 int h2g_params_write(uint64_t params, int format, uint8_t* out, size_t cap, size_t* len) {
@@ -299,11 +372,7 @@ int h2g_pk_write(uint64_t pk_h, int format, uint8_t* out, size_t cap, size_t* le
   HIPCHK(hipStreamSynchronize(d->stream));
   ByteWriter w{out, out ? cap : 0, d->stream};
   w.proc = format == SERDE_PROCESSED;
-  w.u8(PK_VERSION);
-  w.u8((uint8_t)pk.k);
-  w.u32le((uint32_t)pk.F);
-  for (const auto& c : pk.vk_fixed) w.g1(c);
-  for (const auto& c : pk.vk_perm) w.g1(c);  // permutation::VerifyingKey::write
+  vk_write_prefix(w, pk.k, pk.vk_fixed, pk.vk_perm);
   RCCHK(w.poly(pk.l0, pk.ext));
   RCCHK(w.poly(pk.l_last, pk.ext));
   RCCHK(w.poly(pk.l_active, pk.ext));
@@ -331,30 +400,10 @@ int h2g_pk_read(uint64_t params, const h2g_circuit* circuit, const uint8_t* buf,
     return fail(H2G_ERR_ARG, "pk_read: unknown SerdeFormat");
   const bool proc = format == SERDE_PROCESSED;
   ByteReader r{buf, len};
-  if (r.u8() != PK_VERSION) return fail(H2G_ERR_ARG, "pk_read: unexpected version byte");
-  const uint32_t k = r.u8();
-  if (!r.ok || k != circuit->k || k != it->second->k) return fail(H2G_ERR_ARG, "pk_read: k does not match");
-  const uint32_t F = r.u32le();
-  if (!r.ok || F != circuit->num_fixed) return fail(H2G_ERR_ARG, "pk_read: fixed column count does not match");
-  const uint32_t P = circuit->num_perm_columns;
-  std::vector<G1Affine> vf(F), vp(P);
-  bool enc_ok = true;
-  for (auto* v : {&vf, &vp})
-    for (auto& c : *v) {
-      if (proc) {
-        if (const uint8_t* b = r.take(32)) enc_ok = g1_decompress_host(b, &c) && enc_ok;
-      } else if (const uint8_t* b = r.take(sizeof(G1Affine))) {
-        std::memcpy(&c, b, sizeof(G1Affine));
-      }
-    }
-  if (!r.ok) return fail(H2G_ERR_ARG, "pk_read: truncated verifying key");
-  if (!enc_ok) return fail(H2G_ERR_ARG, "pk_read: invalid point encoding in the verifying key");
-  if (format == SERDE_RAW) {
-    for (const auto& c : vf)
-      if (!g1_valid_host(c)) return fail(H2G_ERR_ARG, "pk_read: invalid fixed commitment");
-    for (const auto& c : vp)
-      if (!g1_valid_host(c)) return fail(H2G_ERR_ARG, "pk_read: invalid permutation commitment");
-  }
+  const uint32_t k = circuit->k, F = circuit->num_fixed, P = circuit->num_perm_columns;
+  if (k != it->second->k) return fail(H2G_ERR_ARG, "pk_read: k does not match");
+  std::vector<G1Affine> vf, vp;
+  RCCHK(vk_read_prefix(r, format, circuit, "pk_read", &vf, &vp));
   // the extended domain size follows from the constraint system (keygen::create_domain):
   // taken from the first polynomial here and checked against the keygen's below
   const size_t n = (size_t)1 << k;

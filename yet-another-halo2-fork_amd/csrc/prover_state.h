@@ -1,5 +1,6 @@
 // prover_state.h -- what the prover's translation units share (internal: included only by
-// params.cpp, commit.cpp, keygen.cpp, spmd.cpp, prover.cpp, pk_serde.cpp, check_witness.cpp):
+// params.cpp, commit.cpp, keygen.cpp, spmd.cpp, prover.cpp, pk_serde.cpp, check_witness.cpp,
+// verifier.cpp):
 // the params / proving-key / workspace objects, the library's globals and the prototypes of
 // the functions that cross files.  Each global is defined in the file that owns it.
 #pragma once
@@ -97,6 +98,26 @@ struct Query {
   bool operator==(const Query& o) const { return type == o.type && index == o.index && rot == o.rot; }
 };
 
+// The constraint system as the host sees it: the shape that keygen derives from an h2g_circuit
+// (degree, queries, blinding factors; circuit.rs:143-170,292-320, keygen.rs:191-260) and a
+// copy of its expression graph.  The prover runs the compiled device program; the verifier
+// (verifier.cpp) evaluates these nodes at one point.
+struct CsHost {
+  uint32_t k = 0;
+  int A = 0, F = 0, I = 0, P = 0, NL = 0, NS = 0;
+  int degree = 0, bf = 0, chunk_len = 0, nsets = 0, max_phase = 0;
+  std::vector<Query> adv_q, fix_q, ins_q;
+  std::vector<std::pair<int, int>> perm_cols;
+  std::vector<uint8_t> adv_phase, ch_phase;
+  Fr transcript_repr;
+  std::vector<int32_t> nodes;  // 4 per node (op, a, b, c), children before parents
+  std::vector<Fr> constants;
+  std::vector<int32_t> gate_roots;
+  std::vector<std::vector<int32_t>> lk_in, lk_tab, sh_in, sh_sh;  // per argument, expression roots
+};
+// keygen.cpp: validates the graph and fills `cs`; fails with H2G_ERR_ARG and keygen's messages
+int cs_host_build(const h2g_circuit* c, CsHost* cs);
+
 // Per-circuit workspace of create_proof (one per circuit of a proof over several
 // circuits, grown on demand and reused across proofs): the advice / instance columns,
 // permutation, lookup and shuffle polynomials, and the device pointer tables that
@@ -151,6 +172,7 @@ struct ProvingKey {
   // verifying-key commitments (fixed, permutation) of a key read from bytes; a key made
   // by keygen computes them when it is written (h2g_pk_write)
   std::vector<G1Affine> vk_fixed, vk_perm;
+  CsHost cs;  // the host copy of the constraint system (h2g_vk_from_pk)
   // multi-open scheme of create_proof (the Prover type parameter, prover.rs:19-36):
   // 0 ProverSHPLONK, 1 ProverGWC; GWC witness polynomials, one per opening point
   int multiopen = 0;
@@ -315,6 +337,14 @@ struct ProvingKey {
     bool ready = false;
   } ck;
 };
+
+// VerifyingKey (plonk.rs:42-231) as the verifier needs it: the constraint system and the
+// fixed / permutation commitments, all on the host -- no params, no device arrays
+struct VerifyingKey {
+  CsHost cs;
+  std::vector<G1Affine> fixed, perm;
+};
+extern std::map<uint64_t, std::unique_ptr<VerifyingKey>> g_vks;   // verifier.cpp
 
 extern std::map<uint64_t, std::unique_ptr<Params>> g_params;      // params.cpp
 extern std::map<uint64_t, std::unique_ptr<ProvingKey>> g_pks;     // keygen.cpp

@@ -375,6 +375,17 @@ class Transcript {
     repr(to_canonical(s), r);
     proof_->insert(proof_->end(), r, r + 32);
   }
+  // the verifier's side of write_point (TranscriptRead::read_point absorbs what it decoded):
+  // false for the point at infinity
+  bool common_point(const G1Affine& p) {
+    if (p.x.is_zero() && p.y.is_zero()) return false;
+    uint8_t b[65];
+    b[0] = 1;
+    repr(to_canonical(p.x), b + 1);
+    repr(to_canonical(p.y), b + 33);
+    absorb(b, 65);
+    return true;
+  }
   // false for the point at infinity ("cannot write points at infinity to the transcript")
   bool write_point(const G1Affine& p) {
     if (p.x.is_zero() && p.y.is_zero()) return false;

@@ -137,6 +137,16 @@ _SIGS = {
     "h2g_set_spmd_exchange_async": ([VP, VP], I32),
     "h2g_event_wait": ([VP], I32),
     "h2g_debug_link_delay": ([VP, VP, ctypes.c_double], I32),
+    "h2g_msm_segmented_dev": ([VP, SZ, VP, VP, VP, SZ, VP, VP], I32),
+    "h2g_msm_segmented": ([U64P, SZ, U64P, VP, VP, SZ, U64P], I32),
+    "h2g_vk_from_pk": ([U64, ctypes.POINTER(U64)], I32),
+    "h2g_vk_read": ([VP, ctypes.c_char_p, SZ, I32, ctypes.POINTER(U64)], I32),
+    "h2g_vk_write": ([U64, I32, VP, SZ, ctypes.POINTER(SZ)], I32),
+    "h2g_vk_free": ([U64], I32),
+    "h2g_params_verifier": ([U64, VP], I32),
+    "h2g_verify_proof": ([U64, VP, I32, I32, VP, ctypes.POINTER(ctypes.c_int32)], I32),
+    "h2g_verify_batch": ([U64, VP, I32, I32, VP, SZ, VP, ctypes.POINTER(ctypes.c_int32), U64P], I32),
+    "h2g_verify_stages": ([ctypes.POINTER(ctypes.c_double)], I32),
 }
 
 TRANSCRIPTS = {"blake2b": 0, "keccak256": 1}  # Blake2bWrite / Keccak256Write (h2g_pk_set_transcript)
@@ -635,6 +645,40 @@ def _write_bytes(fn, handle, fmt):
     return buf.raw[: ln.value]
 
 
+def _c_circuit(circ):
+    """(struct h2g_circuit of an h2g_circuit.Circuit, the arrays it points into)"""
+    keep = [np.ascontiguousarray(x) for x in (circ.gate_roots, circ.nodes, circ.constants, circ.perm_array,
+                                              circ.copies, circ.fixed_values, circ.unblinded,
+                                              circ.transcript_repr(), circ.lookup_sizes, circ.lookup_roots,
+                                              circ.shuffle_sizes, circ.shuffle_roots, circ.advice_phase,
+                                              circ.challenge_phase)]
+    roots, nodes, consts, perm, copies, fixed, unb, tr, lks, lkr, shs, shr, aph, chph = keep
+    c = H2gCircuit(circ.k, circ.num_advice, circ.num_fixed, circ.num_instance,
+                   len(roots), _ptr(roots, I32P_), len(nodes), _ptr(nodes, I32P_),
+                   circ.num_constants, _ptr(consts, U64P), len(perm), _ptr(perm, I32P_),
+                   len(copies), _ptr(copies, I32P_), _ptr(fixed, U64P),
+                   _ptr(unb, ctypes.POINTER(ctypes.c_uint8)), _ptr(tr, U64P),
+                   len(circ.lookups), _ptr(lks, ctypes.POINTER(U32)), _ptr(lkr, I32P_),
+                   len(circ.shuffles), _ptr(shs, ctypes.POINTER(U32)), _ptr(shr, I32P_),
+                   _ptr(aph, ctypes.POINTER(ctypes.c_uint8)), circ.num_challenges,
+                   _ptr(chph, ctypes.POINTER(ctypes.c_uint8)))
+    return c, keep
+
+
+class VerifierParams(ctypes.Structure):
+    """struct h2g_verifier_params (include/h2g.h): ParamsVerifierKZG's three points, 40 words"""
+    _fields_ = [("g1", U64 * 8), ("g2", U64 * 16), ("s_g2", U64 * 16)]
+
+
+class VerifyItem(ctypes.Structure):
+    """struct h2g_verify_item (include/h2g.h)"""
+    _fields_ = [("proof", VP), ("proof_len", SZ), ("num_circuits", U32), ("instance", ctypes.POINTER(VP)),
+                ("instance_lens", ctypes.POINTER(VP))]
+
+
+VERIFY_OK, VERIFY_REJECTED, VERIFY_MALFORMED = 1, 0, -1
+
+
 class Params:
     """ParamsKZG resident on the device (g, g_lagrange; g2, s_g2 on the host)."""
 
@@ -676,6 +720,13 @@ class Params:
         b = np.ascontiguousarray(s_g2, dtype=np.uint64)
         check(lib().h2g_params_set_g2(self.handle, p64(a), p64(b)))
 
+    def verifier(self):
+        """ParamsVerifierKZG: (g1, g2, s_g2) as a VerifierParams -- all a verifier needs of the
+        params (they may be closed afterwards)"""
+        vp = VerifierParams()
+        check(lib().h2g_params_verifier(self.handle, ctypes.byref(vp)))
+        return vp
+
     def set_slab(self, lo, hi):
         """fixed-base windows for this rank's point slab [lo, hi) (one proof over several GPUs)"""
         check(lib().h2g_params_set_slab(self.handle, lo, hi))
@@ -700,21 +751,7 @@ class ProvingKey:
         """keygen, or -- with `data` -- ProvingKey::read of serialised bytes (plonk.rs:334-359)"""
         self.params = params
         self.circ = circ
-        keep = [np.ascontiguousarray(x) for x in (circ.gate_roots, circ.nodes, circ.constants, circ.perm_array,
-                                                  circ.copies, circ.fixed_values, circ.unblinded,
-                                                  circ.transcript_repr(), circ.lookup_sizes, circ.lookup_roots,
-                                                  circ.shuffle_sizes, circ.shuffle_roots, circ.advice_phase,
-                                                  circ.challenge_phase)]
-        roots, nodes, consts, perm, copies, fixed, unb, tr, lks, lkr, shs, shr, aph, chph = keep
-        c = H2gCircuit(circ.k, circ.num_advice, circ.num_fixed, circ.num_instance,
-                       len(roots), _ptr(roots, I32P_), len(nodes), _ptr(nodes, I32P_),
-                       circ.num_constants, _ptr(consts, U64P), len(perm), _ptr(perm, I32P_),
-                       len(copies), _ptr(copies, I32P_), _ptr(fixed, U64P),
-                       _ptr(unb, ctypes.POINTER(ctypes.c_uint8)), _ptr(tr, U64P),
-                       len(circ.lookups), _ptr(lks, ctypes.POINTER(U32)), _ptr(lkr, I32P_),
-                       len(circ.shuffles), _ptr(shs, ctypes.POINTER(U32)), _ptr(shr, I32P_),
-                       _ptr(aph, ctypes.POINTER(ctypes.c_uint8)), circ.num_challenges,
-                       _ptr(chph, ctypes.POINTER(ctypes.c_uint8)))
+        c, keep = _c_circuit(circ)
         h = U64()
         if data is None:
             check(lib().h2g_keygen(params.handle, ctypes.byref(c), ctypes.byref(h)))
@@ -920,6 +957,150 @@ class ProvingKey:
         if self.handle:
             lib().h2g_pk_free(self.handle)
             self.handle = 0
+
+
+# ----------------------------------------------------------------------------- verifier
+def instance_columns(wit, circ):
+    """the instance columns of one witness as verify() takes them: instance_lens[i] Montgomery
+    Fr of column i each"""
+    return [np.ascontiguousarray(wit.instance[i][: int(wit.instance_lens[i])], dtype=np.uint64)
+            for i in range(circ.num_instance)]
+
+
+def _instance_array(col):
+    """(m, 4) Montgomery limbs of a column given as such an array or as canonical ints"""
+    if isinstance(col, np.ndarray) and col.dtype == np.uint64:
+        return np.ascontiguousarray(col).reshape(-1, 4)
+    import h2g_circuit as hc
+    vals = [int(v) for v in col]
+    return hc.ints_to_mont(vals).reshape(-1, 4) if vals else np.zeros((0, 4), np.uint64)
+
+
+class VerifyingKey:
+    """VerifyingKey (plonk.rs:42-231) with verify_proof: host memory only; `vp` is the
+    VerifierParams (Params.verifier()) its proofs are checked against."""
+
+    def __init__(self, handle, circ, vp):
+        self.handle = handle
+        self.circ = circ
+        self.vp = vp
+
+    @classmethod
+    def from_pk(cls, pk, vp=None):
+        h = U64()
+        check(lib().h2g_vk_from_pk(pk.handle, ctypes.byref(h)))
+        return cls(h.value, pk.circ, vp if vp is not None else pk.params.verifier())
+
+    @classmethod
+    def read(cls, circ, data, vp, fmt=RAW_BYTES):
+        """VerifyingKey::read (plonk.rs:88-129); the constraint system comes from `circ`"""
+        c, keep = _c_circuit(circ)
+        h = U64()
+        check(lib().h2g_vk_read(ctypes.byref(c), bytes(data), len(data), fmt, ctypes.byref(h)))
+        del keep
+        return cls(h.value, circ, vp)
+
+    def write(self, fmt=RAW_BYTES):
+        """VerifyingKey::write (plonk.rs:73-86) -> bytes: the leading bytes of ProvingKey.write"""
+        return _write_bytes(lib().h2g_vk_write, self.handle, fmt)
+
+    def _items(self, proofs, instances):
+        keep = []
+        items = (VerifyItem * max(len(proofs), 1))()
+        for i, (proof, inst) in enumerate(zip(proofs, instances)):
+            pb = ctypes.create_string_buffer(bytes(proof), max(len(proof), 1))
+            nc = len(inst)
+            ins_arr = (VP * max(nc, 1))()
+            lens_arr = (VP * max(nc, 1))()
+            for c, cols in enumerate(inst):
+                cols = [_instance_array(col) for col in cols]
+                vals = np.concatenate(cols) if cols else np.zeros((0, 4), np.uint64)
+                vals = np.ascontiguousarray(vals if len(vals) else np.zeros((1, 4), np.uint64))
+                lens = np.ascontiguousarray([len(col) for col in cols] or [0], dtype=np.uint32)
+                keep += [vals, lens]
+                ins_arr[c] = vals.ctypes.data
+                lens_arr[c] = lens.ctypes.data
+            keep += [pb, ins_arr, lens_arr]
+            items[i].proof = ctypes.cast(pb, VP)
+            items[i].proof_len = len(proof)
+            items[i].num_circuits = nc
+            items[i].instance = ctypes.cast(ins_arr, ctypes.POINTER(VP))
+            items[i].instance_lens = ctypes.cast(lens_arr, ctypes.POINTER(VP))
+        return items, keep
+
+    def verify(self, proof, instances, multiopen="shplonk", transcript="blake2b"):
+        """h2g_verify_proof -> VERIFY_OK / VERIFY_REJECTED / VERIFY_MALFORMED.  instances: per
+        circuit of the proof, its instance columns (instance_columns(wit, circ), or lists of
+        canonical ints)."""
+        items, keep = self._items([proof], [instances])
+        verdict = ctypes.c_int32(-2)
+        check(lib().h2g_verify_proof(self.handle, ctypes.byref(self.vp), {"shplonk": 0, "gwc": 1}[multiopen],
+                                     TRANSCRIPTS[transcript], items, ctypes.byref(verdict)))
+        del keep
+        return verdict.value
+
+    def verify_batch(self, proofs, instances, multiopen="shplonk", transcript="blake2b", rng_seed=None, rng=None):
+        """h2g_verify_batch -> (verdicts, stats): one verdict per proof; stats = [pairing
+        checks, MSM terms, points decompressed, host ms].  The random factors come from the
+        operating system unless rng (an object with fill_bytes(n)) or rng_seed (32 bytes: the
+        library's ChaCha20, for tests) is given."""
+        n = len(proofs)
+        items, keep = self._items(proofs, instances)
+        verdicts = (ctypes.c_int32 * max(n, 1))(*([-2] * max(n, 1)))
+        stats = (U64 * 4)()
+        rp, native = None, None
+        if rng_seed is not None:
+            r = Rng()
+            native = U64()
+            sd = (ctypes.c_uint8 * 32)(*bytes(rng_seed))
+            check(lib().h2g_rng_chacha20(sd, ctypes.byref(r), ctypes.byref(native)))
+            keep += [r, sd]
+            rp = ctypes.byref(r)
+        elif rng is not None:
+            fb, fr = rng_callbacks(rng)
+            r = Rng(None, fb, fr)
+            keep += [fb, fr, r]
+            rp = ctypes.byref(r)
+        try:
+            check(lib().h2g_verify_batch(self.handle, ctypes.byref(self.vp), {"shplonk": 0, "gwc": 1}[multiopen],
+                                         TRANSCRIPTS[transcript], items, n, rp, verdicts, stats))
+        finally:
+            if native is not None:
+                lib().h2g_rng_free(native.value)
+        del keep
+        return list(verdicts)[:n], list(stats)
+
+    def close(self):
+        if self.handle:
+            lib().h2g_vk_free(self.handle)
+            self.handle = 0
+
+
+def verify_stages():
+    """wall ms of the last verify call: (host, decompression, segmented MSMs, pairing checks)"""
+    ms = (ctypes.c_double * 4)()
+    check(lib().h2g_verify_stages(ms))
+    return tuple(ms)
+
+
+def msm_segmented(bases, scalars, seg_off, index=None):
+    """h2g_msm_segmented: out[s] = sum_{j in [seg_off[s], seg_off[s+1])} scalars[j] *
+    bases[index[j] if index is given else j] -> (nseg, 8) affine, identity = zeros"""
+    bs = np.ascontiguousarray(bases, dtype=np.uint64).reshape(-1, 8)
+    sc = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+    off = np.ascontiguousarray(seg_off, dtype=np.uint32)
+    ix = None if index is None else np.ascontiguousarray(index, dtype=np.uint32)
+    nseg = len(off) - 1
+    out = np.zeros((max(nseg, 1), 8), dtype=np.uint64)
+    check(lib().h2g_msm_segmented(p64(bs) if bs.size else None, len(bs), p64(sc) if sc.size else None,
+                                  ix.ctypes.data_as(VP) if ix is not None and ix.size else None,
+                                  off.ctypes.data_as(VP), nseg, p64(out)))
+    return out[:nseg]
+
+
+def msm_segmented_dev(d_bases, nbases, d_scalars, d_index, d_seg_off, nseg, d_out, stream=None):
+    check(lib().h2g_msm_segmented_dev(VP(d_bases), nbases, VP(d_scalars), VP(d_index) if d_index else None,
+                                      VP(d_seg_off), nseg, VP(d_out), VP(stream) if stream else None))
 
 
 # ----------------------------------------------------------- multi-GPU MSM slabs
