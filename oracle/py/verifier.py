@@ -256,6 +256,13 @@ def verify(circ, instances, proof: bytes, s: int, instance_lens=None, multiopen=
     nsets = (len(circ.perm_columns) + chunk_len - 1) // chunk_len
     insts = instances_multi if instances_multi is not None else [instances]
     NC = len(insts)
+    # Error::InstanceTooLarge: a column may fill the usable rows only (the bound of
+    # verifier.rs:91-93 and of the prover, prover.rs:212-214; like h2g_verify_proof, which
+    # answers MALFORMED, this applies it whatever the scheme's QUERY_INSTANCE)
+    for inst in insts:
+        for col in inst:
+            if len(col) > n - (bf + 1):
+                raise VerifyError("instance too large")
 
     # vk: fixed and permutation commitments, [f(s)]G
     if vk is not None:

@@ -253,6 +253,7 @@ def test_malformed_inputs_are_verdicts_not_errors(base):
     n = kc["circ"].n
     long_col = [[np.zeros((n, 4), dtype=np.uint64)] + list(cols[0][1:])]
     assert vk.verify(proof, long_col) == MALFORMED
+    assert oracle_verdict(kc, proof, long_col) == MALFORMED
     big = [[np.full((1, 4), 0xFFFFFFFFFFFFFFFF, dtype=np.uint64)] + list(cols[0][1:])]
     assert vk.verify(proof, big) == MALFORMED
     # a malformed proof in a batch leaves its neighbours alone
