@@ -188,6 +188,7 @@ int h2g_g1_add_affine(const uint64_t a[8], const uint64_t b[8], uint64_t out[8])
 /* ---- create_proof (BN254 / KZG / SHPLONK, Blake2b transcript) -------------
  * The backend entry points of halo2_backend/src/plonk/{keygen.rs, prover.rs}:
  *   ParamsKZG::{setup, read}   poly/kzg/commitment.rs:64-131,167-267  -> h2g_params_*
+ *   ParamsKZG::{from_parts, downsize}  kzg/commitment.rs:135-154,291-299 -> h2g_params_from_parts / _downsize
  *   keygen_vk + keygen_pk      plonk/keygen.rs:43-190                  -> h2g_keygen
  *   create_proof(params, pk, circuits=[1], instances, rng, transcript)
  *                              plonk/prover.rs:174-899 (ProverSingle)  -> h2g_create_proof
@@ -244,6 +245,35 @@ int h2g_params_free(uint64_t params);
  * before the params can be written */
 int h2g_params_g2(uint64_t params, uint64_t g2[16], uint64_t s_g2[16]);
 int h2g_params_set_g2(uint64_t params, const uint64_t g2[16], const uint64_t s_g2[16]);
+
+/* ---- from a ceremony's monomial powers to params of the circuit's size ----
+ * g_to_lagrange (halo2_backend/src/arithmetic.rs:30-54): n = 2^k G1Affine in (identity = zeros
+ * allowed anywhere), the Lagrange basis L_i = [n^-1] sum_j [omega^(-ij)] g_j out, natural order,
+ * bit-identical to the reference's for every input (a G1 group FFT on the device,
+ * csrc/g1_fft.hip).  k <= 27.  The points are not checked for being on the curve (as with
+ * h2g_params_create); off-curve input gives unspecified points, never a fault.
+ * _dev: device pointers, d_out may equal d_g.  Queued on `stream` (NULL: the library's), but
+ * the call returns only after the work has completed: its scratch (16 * 2^k bytes of
+ * twiddles) is taken for the call and released before it returns; H2G_ERR_NOMEM if it cannot
+ * be had, with nothing left allocated. */
+int h2g_g1_to_lagrange_dev(const void* d_g, uint32_t k, void* d_out, void* stream);
+int h2g_g1_to_lagrange(const uint64_t* g, uint32_t k, uint64_t* out);   /* host copy in / out */
+/* ParamsKZG::from_parts (kzg/commitment.rs:135-154).  g_lagrange == NULL: computed on the
+ * device from g (above); given: stored as it is.  g2 / s_g2: both given (validated as
+ * h2g_params_set_g2 does) or both NULL (params without G2); exactly one is H2G_ERR_ARG.  The G1
+ * points are not checked for being on the curve.  The params have their fixed-base windows
+ * when the call returns. */
+int h2g_params_from_parts(uint32_t k, const uint64_t* g, const uint64_t* g_lagrange,
+                          const uint64_t g2[16], const uint64_t s_g2[16], uint64_t* handle);
+/* ParamsKZG::downsize (kzg/commitment.rs:291-299): a NEW params object of size 2^k <= the
+ * source's (the reference shrinks in place; here the source stays valid and unchanged, keys
+ * made from it keep working, and one resident ceremony SRS serves several circuit sizes):
+ * g truncated (device-to-device), g_lagrange recomputed (also when k is the source's, as the
+ * reference does), g2 / s_g2 carried over (params without G2 give params without G2), own
+ * fixed-base windows; slab windows (h2g_params_set_slab) are not inherited.  k above the
+ * source's: H2G_ERR_ARG; unknown handle: H2G_ERR_HANDLE; params on another device:
+ * H2G_ERR_ARG. */
+int h2g_params_downsize(uint64_t params, uint32_t k, uint64_t* handle);
 
 /* ---- serialisation: SerdeFormat (halo2_backend/src/helpers.rs:8-21) -----------------
  * format 1 RawBytes (uncompressed points, Montgomery limbs; reads check that field

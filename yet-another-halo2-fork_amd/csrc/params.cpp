@@ -1,5 +1,6 @@
 // params.cpp -- the KZG params object: the SRS in both bases, their fixed-base windows,
 // the lookup commitments' prefix basis, and the h2g_params_* entry points.
+#include "g1_fft.h"
 #include "prover_state.h"
 
 using namespace h2g;
@@ -108,6 +109,68 @@ int h2g_params_setup(uint32_t k, const uint64_t s_limbs[4], uint64_t* handle) {
   const Fr s_can = to_canonical(s);
   p->s_g2 = g2_mul(p->g2, s_can.l);
   p->has_g2 = true;
+  *handle = g_next_handle++;
+  g_params[*handle] = std::move(p);
+  return H2G_OK;
+}
+
+/* ParamsKZG::from_parts (kzg/commitment.rs:135-154); g_lagrange == NULL: g_to_lagrange on the device */
+int h2g_params_from_parts(uint32_t k, const uint64_t* g, const uint64_t* g_lagrange, const uint64_t g2[16],
+                          const uint64_t s_g2[16], uint64_t* handle) {
+  NEED_DEV_P();
+  if (!g || !handle || k > G1FFT_MAX_K) return fail(H2G_ERR_ARG, "params_from_parts: bad arguments");
+  if (!g2 != !s_g2) return fail(H2G_ERR_ARG, "params_from_parts: g2 and s_g2 go together (both or neither)");
+  G2Affine a, b;
+  if (g2) {
+    std::memcpy(&a, g2, sizeof(G2Affine));
+    std::memcpy(&b, s_g2, sizeof(G2Affine));
+    if (!g2_valid(a) || !g2_valid(b)) return fail(H2G_ERR_ARG, "params_from_parts: invalid G2 point");
+  }
+  auto p = std::make_unique<Params>();
+  p->device = d->id;
+  p->k = k;
+  p->n = (size_t)1 << k;
+  PALLOC(p->pool, p->g, p->n);
+  PALLOC(p->pool, p->gl, p->n);
+  HIPCHK(hipMemcpy(p->g, g, p->n * sizeof(G1Affine), hipMemcpyHostToDevice));
+  if (g_lagrange)
+    HIPCHK(hipMemcpy(p->gl, g_lagrange, p->n * sizeof(G1Affine), hipMemcpyHostToDevice));
+  else
+    RCCHK(g1_to_lagrange(p->g, k, p->gl, d->stream));
+  if (g2) {
+    p->g2 = a;
+    p->s_g2 = b;
+    p->has_g2 = true;
+  }
+  RCCHK(params_finish(*p, d->stream));
+  *handle = g_next_handle++;
+  g_params[*handle] = std::move(p);
+  return H2G_OK;
+}
+
+/* ParamsKZG::downsize (kzg/commitment.rs:291-299) into a new object; the source is only read */
+int h2g_params_downsize(uint64_t params, uint32_t k, uint64_t* handle) {
+  NEED_DEV_P();
+  if (!handle) return fail(H2G_ERR_ARG, "params_downsize: null handle output");
+  auto it = g_params.find(params);
+  if (it == g_params.end()) return fail(H2G_ERR_HANDLE, "unknown params");
+  const Params& src = *it->second;
+  if (src.device != d->id) return fail(H2G_ERR_ARG, "params_downsize: params live on another device");
+  if (k > src.k || k > G1FFT_MAX_K)
+    return fail(H2G_ERR_ARG, "params_downsize: k = " + std::to_string(k) + " above the params' " + std::to_string(src.k));
+  hipStream_t st = d->stream;
+  auto p = std::make_unique<Params>();
+  p->device = d->id;
+  p->k = k;
+  p->n = (size_t)1 << k;
+  PALLOC(p->pool, p->g, p->n);
+  PALLOC(p->pool, p->gl, p->n);
+  HIPCHK(hipMemcpyAsync(p->g, src.g, p->n * sizeof(G1Affine), hipMemcpyDeviceToDevice, st));
+  RCCHK(g1_to_lagrange(p->g, k, p->gl, st));
+  p->has_g2 = src.has_g2;
+  p->g2 = src.g2;
+  p->s_g2 = src.s_g2;
+  RCCHK(params_finish(*p, st));
   *handle = g_next_handle++;
   g_params[*handle] = std::move(p);
   return H2G_OK;

@@ -1,6 +1,6 @@
 // prover_state.h -- what the prover's translation units share (internal: included only by
 // params.cpp, commit.cpp, keygen.cpp, spmd.cpp, prover.cpp, pk_serde.cpp, check_witness.cpp,
-// verifier.cpp):
+// verifier.cpp, g1_fft.hip):
 // the params / proving-key / workspace objects, the library's globals and the prototypes of
 // the functions that cross files.  Each global is defined in the file that owns it.
 #pragma once

@@ -89,6 +89,10 @@ _SIGS = {
     "h2g_params_free": ([U64], I32),
     "h2g_params_g2": ([U64, U64P, U64P], I32),
     "h2g_params_set_g2": ([U64, U64P, U64P], I32),
+    "h2g_g1_to_lagrange_dev": ([VP, U32, VP, VP], I32),
+    "h2g_g1_to_lagrange": ([U64P, U32, U64P], I32),
+    "h2g_params_from_parts": ([U32, U64P, U64P, U64P, U64P, ctypes.POINTER(U64)], I32),
+    "h2g_params_downsize": ([U64, U32, ctypes.POINTER(U64)], I32),
     "h2g_params_write": ([U64, I32, VP, SZ, ctypes.POINTER(SZ)], I32),
     "h2g_params_read": ([ctypes.c_char_p, SZ, I32, ctypes.POINTER(U64)], I32),
     "h2g_pk_write": ([U64, I32, VP, SZ, ctypes.POINTER(SZ)], I32),
@@ -704,6 +708,29 @@ class Params:
         k = int.from_bytes(bytes(data[:4]), "little")
         return cls(k, _handle=h.value)
 
+    @classmethod
+    def from_parts(cls, k, g, g_lagrange=None, g2=None, s_g2=None):
+        """ParamsKZG::from_parts (kzg/commitment.rs:135-154): g_lagrange None -> computed on
+        the device from g; g2 / s_g2 both given or both None (params without G2)"""
+        h = U64()
+        g = np.ascontiguousarray(g, dtype=np.uint64)
+        if g.size != (8 << k):
+            raise ValueError(f"from_parts: g must hold 2^{k} points")
+        gl = None if g_lagrange is None else np.ascontiguousarray(g_lagrange, dtype=np.uint64)
+        if gl is not None and gl.size != (8 << k):
+            raise ValueError(f"from_parts: g_lagrange must hold 2^{k} points")
+        a = None if g2 is None else np.ascontiguousarray(g2, dtype=np.uint64)
+        b = None if s_g2 is None else np.ascontiguousarray(s_g2, dtype=np.uint64)
+        check(lib().h2g_params_from_parts(k, p64(g), p64(gl), p64(a), p64(b), ctypes.byref(h)))
+        return cls(k, _handle=h.value)
+
+    def downsize(self, k):
+        """ParamsKZG::downsize (kzg/commitment.rs:291-299) -> NEW Params of size 2^k; this
+        object stays valid and unchanged"""
+        h = U64()
+        check(lib().h2g_params_downsize(self.handle, k, ctypes.byref(h)))
+        return Params(k, _handle=h.value)
+
     def write(self, fmt=RAW_BYTES):
         """ParamsKZG::write_custom (kzg/commitment.rs:166-181) -> bytes"""
         return _write_bytes(lib().h2g_params_write, self.handle, fmt)
@@ -1101,6 +1128,22 @@ def msm_segmented(bases, scalars, seg_off, index=None):
 def msm_segmented_dev(d_bases, nbases, d_scalars, d_index, d_seg_off, nseg, d_out, stream=None):
     check(lib().h2g_msm_segmented_dev(VP(d_bases), nbases, VP(d_scalars), VP(d_index) if d_index else None,
                                       VP(d_seg_off), nseg, VP(d_out), VP(stream) if stream else None))
+
+
+def g1_to_lagrange(g):
+    """g_to_lagrange (arithmetic.rs:30-54): (2^k, 8) monomial-basis points -> the Lagrange basis"""
+    g = np.ascontiguousarray(g, dtype=np.uint64).reshape(-1, 8)
+    k = len(g).bit_length() - 1
+    if len(g) != 1 << k:
+        raise ValueError("g1_to_lagrange: the number of points must be a power of two")
+    out = np.zeros_like(g)
+    check(lib().h2g_g1_to_lagrange(p64(g), k, p64(out)))
+    return out
+
+
+def g1_to_lagrange_dev(d_g, k, d_out, stream=None):
+    """the same on device pointers (d_out may equal d_g); returns when the result is ready"""
+    check(lib().h2g_g1_to_lagrange_dev(VP(d_g), k, VP(d_out), VP(stream) if stream else None))
 
 
 # ----------------------------------------------------------- multi-GPU MSM slabs
