@@ -503,6 +503,92 @@ int h2g_verify_batch(uint64_t vk, const h2g_verifier_params* vp, int multiopen, 
  * MSMs (uploads, kernels, results), [3] pairing checks */
 int h2g_verify_stages(double ms[4]);
 
+/* ---- the polynomial-commitment layer on its own (halo2_backend/src/poly/{commitment,query}.rs,
+ * poly/kzg/**, transcript.rs, arithmetic.rs): for a host that opens polynomials of its own over
+ * the resident SRS -- an aggregation layer, a protocol of its own, a shim implementing the
+ * reference's Prover / Verifier traits.  create_proof and verify_proof run the same SHPLONK and
+ * GWC code (csrc/multiopen.cpp).
+ *
+ * Transcript objects: Blake2bWrite / Blake2bRead / Keccak256Write / Keccak256Read
+ * (transcript.rs:291-463; Challenge255).  Host only, usable before h2g_init; `kind` takes the
+ * codes of h2g_pk_set_transcript.  H2G_ERR_ARG is what the reference answers with an io::Error:
+ * the identity as a point, a read past the end, an encoding with x >= p or off the curve, a
+ * scalar >= r -- and a call in the wrong mode.  A failed call leaves the transcript as it was.
+ * Points are affine Montgomery limbs (the ABI's G1Affine); the byte stream carries them compressed.
+ * read_point decompresses on the host. */
+int h2g_transcript_new_write(int kind, uint64_t* t);
+int h2g_transcript_new_read(int kind, const uint8_t* proof, size_t len, uint64_t* t);  /* copies the bytes */
+int h2g_transcript_common_point(uint64_t t, const uint64_t p[8]);    /* Transcript::common_point, either mode */
+int h2g_transcript_common_scalar(uint64_t t, const uint64_t s[4]);
+int h2g_transcript_write_point(uint64_t t, const uint64_t p[8]);     /* TranscriptWrite, write mode only */
+int h2g_transcript_write_scalar(uint64_t t, const uint64_t s[4]);
+int h2g_transcript_read_point(uint64_t t, uint64_t p[8]);            /* TranscriptRead, read mode only */
+int h2g_transcript_read_scalar(uint64_t t, uint64_t s[4]);
+int h2g_transcript_squeeze(uint64_t t, uint64_t c[4]);               /* squeeze_challenge_scalar */
+int h2g_transcript_bytes(uint64_t t, uint8_t* out, size_t cap, size_t* len);  /* finalize() of a write-mode transcript (it stays usable); out == NULL: the length */
+int h2g_transcript_remaining(uint64_t t, size_t* bytes);             /* read mode: unread bytes */
+int h2g_transcript_free(uint64_t t);
+
+/* ParamsKZG::commit / commit_lagrange (poly/kzg/commitment.rs:305-317,354-366): the params'
+ * fixed-base MSM over the prefix [0, len) of g / g_lagrange.  len above the params' n is
+ * H2G_ERR_ARG (the reference's assert!), len == 0 the identity.  _dev: device scalars (16-byte
+ * aligned) read on `stream`; the result comes to the host (synchronous, as h2g_msm_dev_host).
+ * Like h2g_params_msm_dev these are plain local MSMs: an installed shard or SPMD transport
+ * takes no part. */
+int h2g_params_commit(uint64_t params, const uint64_t* coeffs, size_t len, uint64_t out[8], int* is_identity);
+int h2g_params_commit_lagrange(uint64_t params, const uint64_t* evals, size_t len, uint64_t out[8], int* is_identity);
+int h2g_params_commit_dev(uint64_t params, const void* d_coeffs, size_t len, uint64_t out[8], int* is_identity,
+                          void* stream);
+int h2g_params_commit_lagrange_dev(uint64_t params, const void* d_evals, size_t len, uint64_t out[8],
+                                   int* is_identity, void* stream);
+/* eval_polynomial (arithmetic.rs:57-82): out = sum_i poly[i] x^i (len == 0: zero).  Synchronous. */
+int h2g_fr_eval(const uint64_t* poly, size_t len, const uint64_t x[4], uint64_t out[4]);
+int h2g_fr_eval_dev(const void* d_poly, size_t len, const uint64_t x[4], uint64_t out[4], void* stream);
+/* kate_division (arithmetic.rs:101-120): q = (a - a(b)) / (X - b), len - 1 coefficients; len == 1
+ * writes nothing, len == 0 is H2G_ERR_ARG (the reference's subtraction overflows).  _dev:
+ * asynchronous on `stream`, d_q must not overlap d_a, both 16-byte aligned. */
+int h2g_kate_division(const uint64_t* a, size_t len, const uint64_t b[4], uint64_t* q);
+int h2g_kate_division_dev(const void* d_a, size_t len, const uint64_t b[4], void* d_q, void* stream);
+
+/* The multi-open argument.  A polynomial is in coefficient form, 1 <= len <= the params' n, in
+ * host memory or (on_device) device memory, 16-byte aligned.  A query names its polynomial by
+ * index -- the reference's pointer equality of ProverQuery -- and KZG ignores ProverQuery.blind,
+ * so there is no such field.  The order of the queries is part of the argument (SHPLONK's
+ * commitment and rotation-set order, GWC's point groups in first-appearance order) and is kept.
+ * A repeated (polynomial, point) pair does what construct_intermediate_sets does: SHPLONK
+ * (shplonk.rs:48-140) keeps one entry per pair (its sets are maps); GWC (gwc.rs:25-50) lists the
+ * polynomial in the point's group once per occurrence, and so does the verifier.  (If a
+ * verifier's caller gives one pair two different evaluations, SHPLONK uses the later one, as
+ * h2g_verify_proof does; the reference's get_eval finds the first.) */
+typedef struct { const uint64_t* coeffs; size_t len; int on_device; } h2g_poly_ref;
+typedef struct { uint32_t poly; uint32_t reserved; uint64_t point[4]; } h2g_open_query;
+/* Prover::create_proof (poly/commitment.rs:141-168): scheme 0 ProverSHPLONK
+ * (shplonk/prover.rs:121-305), 1 ProverGWC (gwc/prover.rs:40-90).  Evaluates the queries on the
+ * device, then squeezes from and writes into `transcript` (write mode) exactly what the
+ * reference does: SHPLONK y, v, [h], u, [h']; GWC v, one [W] per point group.
+ * A commitment that is the identity cannot enter the transcript (one constant polynomial opened
+ * at one point: h(X) = 0): H2G_ERR_ARG as the reference's Err, and the transcript is left as
+ * it was before the call.  H2G_ERR_ARG also for nqueries == 0, an index out of range, len == 0 or
+ * len > n, a point >= r, a missing pointer, a misaligned device polynomial, a read-mode
+ * transcript.  While a shard or SPMD transport is installed the call returns H2G_ERR_STATE (the
+ * commitments' MSMs would be cut into the transport's slabs).  Scratch (4 n Fr and the GWC
+ * witnesses) is kept with the params. */
+int h2g_multiopen_prove(uint64_t params, int scheme, uint64_t transcript, const h2g_poly_ref* polys, size_t npolys,
+                        const h2g_open_query* queries, size_t nqueries);
+typedef struct { uint32_t commitment; uint32_t reserved; uint64_t point[4]; uint64_t eval[4]; } h2g_verify_query;
+/* Verifier::verify_proof (poly/commitment.rs:171-193; shplonk/verifier.rs:45-140,
+ * gwc/verifier.rs:42-123) + DualMSM::check (kzg/msm.rs:188-206): `commitments` are
+ * ncommitments x 8 u64 affine points (VerifierQuery::new_commitment; MSM-valued commitments are
+ * not offered), the argument's points are read from `transcript` (read mode).
+ * *verdict: H2G_VERIFY_OK / _REJECTED / _MALFORMED (a point of the argument that does not
+ * decode or is the identity, or the bytes end).  lr (may be NULL; written for OK and REJECTED):
+ * the DualMSM's (left, right), affine, for a host that defers or aggregates the pairing: the
+ * proof holds iff e(left, s_g2) = e(right, g2).  H2G_ERR_ARG for bad arguments as above, a
+ * commitment off the curve, a point or evaluation >= r. */
+int h2g_multiopen_verify(const h2g_verifier_params* vp, int scheme, uint64_t transcript,
+                         const uint64_t* commitments, size_t ncommitments,
+                         const h2g_verify_query* queries, size_t nqueries, int32_t* verdict, uint64_t lr[16]);
+
 /* wall milliseconds of the stages of the last h2g_create_proof (names: h2g_prover_stage_name).
  * Stages end when their work is queued, unless h2g_prover_stage_sync(1) is set: then each
  * stage boundary synchronises the prover stream and the times are GPU completion times

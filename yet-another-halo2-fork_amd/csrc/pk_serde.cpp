@@ -173,6 +173,7 @@ namespace prv {
 bool g2_valid(const G2Affine& a) {
   return fq_below(a.x.c0) && fq_below(a.x.c1) && fq_below(a.y.c0) && fq_below(a.y.c1) && g2_on_curve(a);
 }
+bool g1_from_bytes_host(const uint8_t c[32], G1Affine* out) { return g1_decompress_host(c, out); }
 }  // namespace prv
 }  // namespace h2g
 

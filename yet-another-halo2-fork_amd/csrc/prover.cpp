@@ -9,12 +9,12 @@
 //   permutation_commit/evaluate    plonk/permutation/prover.rs:50-333
 //   vanishing commit/construct     plonk/vanishing/prover.rs:40-205
 //   evaluate_h                     plonk/evaluation.rs:317-483
-//   SHPLONK                        poly/kzg/multiopen/shplonk/prover.rs:121-305, shplonk.rs:48-140
+//   SHPLONK / GWC                  poly/kzg/multiopen/** -- multiopen.cpp, run over ProofRun::multiopen_ctx()
 // Host work is the transcript, the prover RNG's few hundred draws, query bookkeeping
 // and O(#queries^2) interpolation; every length-n or extended-length operation is a
 // kernel (MSM, NTT, prover_kernels.hip, poly.hip).  MSM results come back to the host
 // (they enter the transcript), which is the only per-step synchronisation.
-#include "prover_state.h"
+#include "multiopen.h"
 
 using namespace h2g;
 using namespace h2g::rt;
@@ -26,45 +26,8 @@ bool g_stage_sync = false;  // h2g_prover_stage_sync: stage times = GPU completi
 std::vector<Fr> g_last_challenges;  // the challenges of the last proof (h2g_last_challenges)
 
 // ------------------------------------------------------------------ host field helpers
-int fr_cmp(const Fr& a, const Fr& b) {  // Ord on Fr: canonical numeric order
-  const Fr ca = to_canonical(a), cb = to_canonical(b);
-  for (int i = 7; i >= 0; i--) {
-    if (ca.l[i] < cb.l[i]) return -1;
-    if (ca.l[i] > cb.l[i]) return 1;
-  }
-  return 0;
-}
 Fr rotate_omega(const Domain& d, const Fr& x, int rot) {
   return x * pow_u64(rot >= 0 ? d.omega : d.omega_inv, (uint64_t)(rot >= 0 ? rot : -rot));
-}
-
-// the Lagrange basis of the points: out[j] = coefficients of prod_{k != j} (X - p_k) / (p_j - p_k)
-std::vector<std::vector<Fr>> lagrange_basis(const std::vector<Fr>& pts) {
-  const size_t m = pts.size();
-  std::vector<std::vector<Fr>> out(m);
-  for (size_t j = 0; j < m; j++) {
-    std::vector<Fr> num(1, Fr::one());
-    Fr den = Fr::one();
-    for (size_t k = 0; k < m; k++) {
-      if (k == j) continue;
-      std::vector<Fr> nn(num.size() + 1, Fr::zero());
-      for (size_t i = 0; i < num.size(); i++) {
-        nn[i + 1] = nn[i + 1] + num[i];
-        nn[i] = nn[i] - pts[k] * num[i];
-      }
-      num.swap(nn);
-      den = den * (pts[j] - pts[k]);
-    }
-    const Fr sc = inv(den);
-    for (Fr& c : num) c = c * sc;
-    out[j] = std::move(num);
-  }
-  return out;
-}
-Fr eval_host(const std::vector<Fr>& p, const Fr& x) {
-  Fr acc = Fr::zero();
-  for (size_t i = p.size(); i-- > 0;) acc = acc * x + p[i];
-  return acc;
 }
 
 // Debug aid: a build with -DH2G_DUMP_DIR='"<dir>"' writes named intermediates (raw Fr
@@ -90,65 +53,7 @@ void dump(const char* name, const Fr* dptr, size_t count, hipStream_t st, bool h
 #endif
 }
 
-// The kate divisions' carries: for a_i (global indexing, valid on [lo, hi1)) and point b_i,
-// carry[i] = q_i[hi'] = sum_{j >= hi'} a_i[j + 1] b_i^(j - hi') (hi' = min(hi, n - 1)), from
-// every slab's partial Horner value E_s = sum_{j in [lo_s, hi'_s)} a_i[j + 1] b_i^(j - lo_s):
-// C_{W-1} = 0, C_r = E_{r+1} + b^(hi'_{r+1} - lo_{r+1}) C_{r+1}.  One all-gather for all points.
-template <class Buf>
-int slab_carries(ProvingKey& pk, const Slab& sl, size_t n, const std::vector<Fr>& pts, Buf a, std::vector<Fr>* carry,
-                 hipStream_t st) {
-  const size_t np = pts.size();
-  const size_t hq = std::min(sl.hi, n - 1);
-  const uint64_t m = hq > sl.lo ? hq - sl.lo : 0;
-  std::vector<EvalReq> reqs(np);
-  for (size_t i = 0; i < np; i++) reqs[i] = EvalReq{a(i) + sl.lo + 1, m, pts[i]};
-  if ((int)np > pk.max_reqs) {
-    PALLOC(pk.pool, pk.d_reqs, np);
-    PALLOC(pk.pool, pk.evals, np);
-    pk.max_reqs = (int)np;
-  }
-  const size_t need = poly_eval_scratch_len((int)np, m ? m : 1);
-  if (need > pk.eval_scr_len) {
-    PALLOC(pk.pool, pk.eval_scr, need);
-    pk.eval_scr_len = need;
-  }
-  HIPCHK(pk_upload(pk, pk.d_reqs, reqs.data(), np * sizeof(EvalReq), st));
-  HIPCHK(poly_eval_batch(pk.d_reqs, (int)np, m ? m : 1, pk.evals, pk.eval_scr, st));
-  std::vector<Fr> mine(np);
-  HIPCHK(hipMemcpyAsync(mine.data(), pk.evals, np * sizeof(Fr), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  std::vector<Fr> all;
-  RCCHK(spmd_allgather_fr(mine, &all));
-  carry->assign(np, Fr::zero());
-  for (size_t i = 0; i < np; i++) {
-    Fr c = Fr::zero();
-    for (int s = g_spmd.world - 1; s > g_spmd.rank; s--) {
-      const Slab ss = spmd_slab(n, s);
-      const size_t hs = std::min(ss.hi, n - 1);
-      const uint64_t ms = hs > ss.lo ? hs - ss.lo : 0;
-      c = all[(size_t)s * np + i] + pow_u64(pts[i], ms) * c;
-    }
-    (*carry)[i] = c;
-  }
-  return H2G_OK;
-}
-
 // ------------------------------------------------------------------ create_proof
-// A proof that fails part-way leaves launched MSMs uncollected: their result ring entries
-// would stay reserved.  Proofs run one at a time under the library lock and collect every
-// MSM they launch, so on the way out the MSM streams are drained and the ring freed.
-struct MsmRingGuard {
-  Device* d;
-  ~MsmRingGuard() {
-    bool any = false;
-    for (bool b : d->ring_busy) any = any || b;
-    if (!any) return;
-    for (hipStream_t s : d->mstream)
-      if (s) (void)hipStreamSynchronize(s);
-    for (bool& b : d->ring_busy) b = false;
-  }
-};
-
 struct StageClock {
   std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
   hipStream_t st;
@@ -160,11 +65,6 @@ struct StageClock {
     g_stages.emplace_back(name, std::chrono::duration<double, std::milli>(t - t0).count());
     t0 = t;
   }
-};
-
-struct PolyRef {  // a committed polynomial in coefficient form (SHPLONK's "commitment identity")
-  const Fr* p;
-  uint64_t len;
 };
 
 // the proof's upload staging (ProvingKey::up_h): armed behind a sync of the prover's
@@ -493,13 +393,9 @@ struct ProofRun {
   int id_lk(int ci) const { return ci * per_c + pk.A + pk.nsets; }  // lookup l: z, A', S' at + 3 l
   int id_sh(int ci) const { return ci * per_c + pk.A + pk.nsets + 3 * pk.NL; }
   std::vector<PolyRef> polys;
-  struct Q2 {
-    int poly;
-    Fr pt;
-  };
-  std::vector<Q2> queries;
+  std::vector<OpenQ> queries;
   // unique (poly, point) evaluations, one batched launch
-  std::vector<Q2> ev_keys;
+  std::vector<OpenQ> ev_keys;
   std::vector<std::vector<int>> ev_of;  // per polynomial its ev_keys entries (a few points)
   int ev_index(int poly, const Fr& pt) {
     if ((size_t)poly >= ev_of.size()) ev_of.resize((size_t)poly + 1);
@@ -549,6 +445,7 @@ struct ProofRun {
   int eval_h();
   int h_commit();
   int openings_and_evals();
+  MultiopenCtx multiopen_ctx();
   int gwc();
   int shplonk();
 };
@@ -1709,289 +1606,35 @@ int ProofRun::openings_and_evals() {
   return H2G_OK;
 }
 
-// ---- ProverGWC::create_proof_with_engine (gwc/prover.rs:40-90): the queries grouped
-// by point in first-appearance order (construct_intermediate_sets, gwc.rs:25-50); per
-// point W(X) = (sum_i v^i p_i(X) - sum_i v^i p_i(z)) / (X - z), committed against g.
-// The points' MSMs are independent, so all are launched before the first is collected.
-int ProofRun::gwc() {
-  const Fr v = tr.squeeze();
-  std::vector<char> done(queries.size(), 0);
-  std::vector<MsmTicket> tk;
-  std::vector<Fr> neg_evb;
-  neg_evb.reserve(queries.size());
-  for (size_t i = 0; i < queries.size(); i++) {
-    if (done[i]) continue;
-    const Fr z = queries[i].pt;
-    const size_t g = tk.size();
-    if (g >= pk.gwc_q.size()) {
-      Fr* q;
-      PALLOC(pk.pool, q, n);
-      pk.gwc_q.push_back(q);
-    }
-    LinTerms t;
-    bool first = true;
-    Fr vp = Fr::one(), evb = Fr::zero();
-    for (size_t j = i; j < queries.size(); j++) {
-      if (done[j] || queries[j].pt != z) continue;
-      done[j] = 1;
-      if (t.k == LIN_MAXT - 1) {
-        HIPCHK(lincomb(pk.nx, n, t, !first, st));
-        first = false;
-        t.k = 0;
-      }
-      t.p[t.k] = polys[queries[j].poly].p;
-      t.len[t.k] = polys[queries[j].poly].len;
-      t.coef[t.k] = vp;
-      t.k++;
-      evb = evb + vp * ev(queries[j].poly, z);
-      vp = vp * v;
-    }
-    neg_evb.push_back(Fr::zero() - evb);  // poly_batch - eval_batch (poly.rs:268-276)
-    HIPCHK(pk_upload(pk, pk.small + g, &neg_evb.back(), sizeof(Fr), st));
-    t.p[t.k] = pk.small + g;
-    t.len[t.k] = 1;
-    t.coef[t.k] = Fr::one();
-    t.k++;
-    HIPCHK(lincomb(pk.nx, n, t, !first, st));
-    HIPCHK(kate_division(pk.nx, n, z, pk.gwc_q[g], pk.scr, st));
-    tk.emplace_back();
-    RCCHK(commit_launch(d, prm, pk.gwc_q[g], n - 1, SRS_G, st, &tk.back()));  // commit (kzg/commitment.rs:354-366)
-  }
-  {
-    std::vector<MsmTicket*> tl;
-    for (auto& t : tk) tl.push_back(&t);
-    RCCHK(collect_write(tl));
-  }
-  HIPCHK(hipStreamSynchronize(st));  // neg_evb (host) is read by the copies above
-  clk.mark("gwc");
-  return H2G_OK;
+// ---- the multi-open argument (multiopen.cpp) over this proof's polynomials, queries and
+// evaluations, with the proving key's scratch
+MultiopenCtx ProofRun::multiopen_ctx() {
+  MultiopenCtx c;
+  c.d = d;
+  c.prm = &prm;
+  c.st = st;
+  c.tr = &tr;
+  c.n = n;
+  c.polys = &polys;
+  c.queries = &queries;
+  c.ev = [this](int poly, const Fr& pt) { return ev(poly, pt); };
+  c.nx = pk.nx, c.hx = pk.hx, c.lx = pk.lx, c.q1 = pk.q1, c.scr = pk.scr, c.small = pk.small;
+  c.gwc_q = &pk.gwc_q;
+  c.pool = &pk.pool;
+  c.upload = [this](void* dst, const void* src, size_t bytes) { return pk_upload(pk, dst, src, bytes, st); };
+  c.mark = [this](const char* name) { clk.mark(name); };
+  c.slabs = slabs;
+  c.sl = sl;
+  c.slab_pk = &pk;
+  return c;
 }
-
-// ---- SHPLONK (shplonk/prover.rs:121-305; construct_intermediate_sets shplonk.rs:48-140)
+int ProofRun::gwc() {
+  MultiopenCtx c = multiopen_ctx();
+  return multiopen_gwc(c);
+}
 int ProofRun::shplonk() {
-  // host values the device copies read asynchronously (live until the proof returns)
-  std::vector<std::vector<Fr>> corr_stage;
-  Fr c0_stage;
-  StreamSyncGuard corr_guard{st};
-  const Fr sy = tr.squeeze();
-  std::vector<Fr> super_pts;
-  for (auto& q : queries) {
-    bool f = false;
-    for (auto& p : super_pts) f = f || p == q.pt;
-    if (!f) super_pts.push_back(q.pt);
-  }
-  std::sort(super_pts.begin(), super_pts.end(), [](const Fr& a, const Fr& b) { return fr_cmp(a, b) < 0; });
-  std::vector<int> cm_ids;
-  std::vector<std::vector<Fr>> cm_pts;
-  for (auto& q : queries) {
-    int f = -1;
-    for (size_t i = 0; i < cm_ids.size(); i++)
-      if (cm_ids[i] == q.poly) f = (int)i;
-    if (f < 0) {
-      f = (int)cm_ids.size();
-      cm_ids.push_back(q.poly);
-      cm_pts.emplace_back();
-    }
-    auto& ps = cm_pts[f];
-    if (std::find(ps.begin(), ps.end(), q.pt) == ps.end()) ps.push_back(q.pt);
-  }
-  for (auto& ps : cm_pts) std::sort(ps.begin(), ps.end(), [](const Fr& a, const Fr& b) { return fr_cmp(a, b) < 0; });
-  std::vector<int> rs_of(cm_ids.size()), rs_rep;
-  for (size_t c = 0; c < cm_ids.size(); c++) {
-    int f = -1;
-    for (size_t r = 0; r < rs_rep.size(); r++)
-      if (cm_pts[rs_rep[r]] == cm_pts[c]) f = (int)r;
-    if (f < 0) {
-      f = (int)rs_rep.size();
-      rs_rep.push_back((int)c);
-    }
-    rs_of[c] = f;
-  }
-  // r_c: the interpolation through c's evaluations, from its rotation set's Lagrange basis
-  // (one set of inversions per set, not per commitment)
-  std::vector<std::vector<std::vector<Fr>>> basis(rs_rep.size());
-  for (size_t r = 0; r < rs_rep.size(); r++) basis[r] = lagrange_basis(cm_pts[rs_rep[r]]);
-  std::vector<std::vector<Fr>> low(cm_ids.size());
-  for (size_t c = 0; c < cm_ids.size(); c++) {
-    const auto& B = basis[rs_of[c]];
-    const size_t m = cm_pts[c].size();
-    low[c].assign(m, Fr::zero());
-    for (size_t j = 0; j < m; j++) {
-      const Fr e = ev(cm_ids[c], cm_pts[c][j]);
-      for (size_t i = 0; i < m; i++) low[c][i] = low[c][i] + B[j][i] * e;
-    }
-  }
-  const Fr v = tr.squeeze();
-  // h_x = sum_s v^s (sum_i y^i (p_i - r_i)) / Z_s (the reference divides by Z_s with one
-  // kate division per point of S_s, shplonk/prover.rs:142-176).  Partial fractions instead:
-  // 1 / Z_s = sum_{p in S_s} c_{s,p} / (X - p) with c_{s,p} = prod_{p' in S_s \ p} (p - p')^-1,
-  // and (g_s - r_s) / (X - p) is exact for every p in S_s, so with
-  // G_p = sum_{s : p in S_s} v^s c_{s,p} (g_s - r_s), h_x = sum_p G_p / (X - p): one kate
-  // division per distinct point (accumulated into h_x) instead of one per (set, point).
-  // Exact field arithmetic, so h_x is the same polynomial.
-  {
-    std::vector<Fr> vpow(rs_rep.size()), ypow(cm_ids.size());
-    {
-      Fr vp = Fr::one();
-      for (size_t r = 0; r < rs_rep.size(); r++) {
-        vpow[r] = vp;
-        vp = vp * v;
-        Fr yp = Fr::one();
-        for (size_t c = 0; c < cm_ids.size(); c++)
-          if (rs_of[c] == (int)r) {
-            ypow[c] = yp;
-            yp = yp * sy;
-          }
-      }
-    }
-    // slab mode: per point a (slab + halo) buffer; gbuf(i) indexes it globally
-    const size_t np = super_pts.size(), cap = sl.hi1 - sl.lo + 1;
-    if (slabs && np * cap > pk.slab_buf_len) {
-      PALLOC(pk.pool, pk.slab_buf, np * cap);
-      pk.slab_buf_len = np * cap;
-    }
-    auto gbuf = [&](size_t i) { return pk.slab_buf + i * cap - sl.lo; };
-    if (slabs) HIPCHK(hipMemsetAsync(pk.hx + sl.lo, 0, (sl.hi1 - sl.lo) * sizeof(Fr), st));
-    else HIPCHK(hipMemsetAsync(pk.hx, 0, n * sizeof(Fr), st));
-    for (size_t pi = 0; pi < np; pi++) {
-      const Fr& p = super_pts[pi];
-      Fr* gp = slabs ? gbuf(pi) : pk.nx;
-      // alpha_s = v^s c_{s,p} for the sets containing p
-      std::vector<Fr> alpha(rs_rep.size(), Fr::zero());
-      std::vector<char> has(rs_rep.size(), 0);
-      size_t ncorr = 0;
-      for (size_t r = 0; r < rs_rep.size(); r++) {
-        const std::vector<Fr>& pts = cm_pts[rs_rep[r]];
-        if (std::find(pts.begin(), pts.end(), p) == pts.end()) continue;
-        Fr den = Fr::one();
-        for (const Fr& q : pts)
-          if (!(q == p)) den = den * (p - q);
-        alpha[r] = vpow[r] * inv(den);
-        has[r] = 1;
-        ncorr = std::max(ncorr, pts.size());
-      }
-      corr_stage.emplace_back(ncorr, Fr::zero());  // read by an async copy
-      std::vector<Fr>& corr = corr_stage.back();
-      LinTerms t;
-      bool first = true;
-      for (size_t c = 0; c < cm_ids.size(); c++) {
-        const int r = rs_of[c];
-        if (!has[r]) continue;
-        if (t.k == LIN_MAXT - 1) {
-          RCCHK(lincomb_range(gp, sl.lo, sl.hi1, t, !first, st));
-          first = false;
-          t.k = 0;
-        }
-        const Fr coef = alpha[r] * ypow[c];
-        t.p[t.k] = polys[cm_ids[c]].p;
-        t.len[t.k] = polys[cm_ids[c]].len;
-        t.coef[t.k] = coef;
-        t.k++;
-        for (size_t j = 0; j < low[c].size(); j++) corr[j] = corr[j] + coef * low[c][j];
-      }
-      HIPCHK(pk_upload(pk, pk.small, corr.data(), corr.size() * sizeof(Fr), st));
-      t.p[t.k] = pk.small;
-      t.len[t.k] = corr.size();
-      t.coef[t.k] = fr_neg_one();
-      t.k++;
-      RCCHK(lincomb_range(gp, sl.lo, sl.hi1, t, !first, st));
-      if (!slabs) HIPCHK(kate_division(pk.nx, n, p, pk.hx, pk.scr, st, true));
-    }
-    if (slabs) {
-      // G_p / (X - p) on slabs: q[i] = sum_{j >= i} a[j + 1] p^(j - i).  The slab's own part
-      // plus p^(hi' - i) C, with C = q[hi'] the quotient just above the slab = sum over the
-      // higher slabs of their partial Horner values E_s (one all-gather for every point);
-      // C enters as p C added to a[hi'], so the division runs unchanged on the slab.
-      std::vector<Fr> carry;
-      RCCHK(slab_carries(pk, sl, n, super_pts, [&](size_t i) { return gbuf(i); }, &carry, st));
-      Fr halo = Fr::zero();
-      for (size_t pi = 0; pi < np; pi++) {
-        const size_t hq = std::min(sl.hi, n - 1);
-        if (hq <= sl.lo) continue;
-        HIPCHK(poly_binop(POLY_ADD_CONST, gbuf(pi) + hq, nullptr, super_pts[pi] * carry[pi], gbuf(pi) + hq, 1, st));
-        HIPCHK(kate_division(gbuf(pi) + sl.lo, hq - sl.lo + 1, super_pts[pi], pk.hx + sl.lo, pk.scr, st, true));
-        halo = halo + carry[pi];
-      }
-      if (sl.hi < n) {  // h_x's halo coefficient (read by the linearisation): q[hi] = sum of the carries
-        corr_stage.emplace_back(1, halo);
-        HIPCHK(pk_upload(pk, pk.hx + sl.hi, corr_stage.back().data(), sizeof(Fr), st));
-      }
-    }
-  }
-  {
-    G1Affine cm;
-    RCCHK(commit(d, prm, pk.hx, n, SRS_G, &cm, st));
-    RCCHK(write_point(cm));
-  }
-  clk.mark("shplonk h");
-  const Fr u = tr.squeeze();
-  // linearisation: l_x = sum_s v^s Z_{T\S_s}(u) sum_i y^i (p_i - r_i(u)) - Z_T(u) h_x
-  Fr z0 = Fr::one();
-  {
-    Fr vpow = Fr::one(), c0 = Fr::zero();
-    LinTerms t;
-    bool first = true;
-    auto flush = [&]() -> int {
-      RCCHK(lincomb_range(pk.lx, sl.lo, sl.hi1, t, !first, st));  // a slab rank: slab + halo
-      first = false;
-      t.k = 0;
-      return H2G_OK;
-    };
-    for (size_t r = 0; r < rs_rep.size(); r++) {
-      const std::vector<Fr>& pts = cm_pts[rs_rep[r]];
-      Fr zi = Fr::one();
-      for (auto& sp : super_pts)
-        if (std::find(pts.begin(), pts.end(), sp) == pts.end()) zi = (u - sp) * zi;
-      if (r == 0) z0 = zi;
-      Fr ypow = Fr::one();
-      for (size_t c = 0; c < cm_ids.size(); c++) {
-        if (rs_of[c] != (int)r) continue;
-        if (t.k == LIN_MAXT - 2) RCCHK(flush());
-        const Fr coef = ypow * zi * vpow;
-        t.p[t.k] = polys[cm_ids[c]].p;
-        t.len[t.k] = polys[cm_ids[c]].len;
-        t.coef[t.k] = coef;
-        t.k++;
-        c0 = c0 - coef * eval_host(low[c], u);
-        ypow = ypow * sy;
-      }
-      vpow = vpow * v;
-    }
-    Fr zt = Fr::one();
-    for (auto& sp : super_pts) zt = (u - sp) * zt;
-    c0_stage = c0;
-    HIPCHK(pk_upload(pk, pk.small, &c0_stage, sizeof(Fr), st));
-    t.p[t.k] = pk.small;
-    t.len[t.k] = 1;
-    t.coef[t.k] = Fr::one();
-    t.k++;
-    t.p[t.k] = pk.hx;
-    t.len[t.k] = n;
-    t.coef[t.k] = Fr::zero() - zt;
-    t.k++;
-    RCCHK(flush());
-  }
-  if (slabs) {  // the same slab division by (X - u), one carry
-    std::vector<Fr> carry;
-    const std::vector<Fr> pts{u};
-    RCCHK(slab_carries(pk, sl, n, pts, [&](size_t) { return pk.lx; }, &carry, st));
-    const size_t hq = std::min(sl.hi, n - 1);
-    if (hq > sl.lo) {
-      HIPCHK(poly_binop(POLY_ADD_CONST, pk.lx + hq, nullptr, u * carry[0], pk.lx + hq, 1, st));
-      HIPCHK(kate_division(pk.lx + sl.lo, hq - sl.lo + 1, u, pk.q1 + sl.lo, pk.scr, st));
-      HIPCHK(poly_binop(POLY_SCALE, pk.q1 + sl.lo, nullptr, inv(z0), pk.q1 + sl.lo, hq - sl.lo, st));
-    }
-  } else {
-    HIPCHK(kate_division(pk.lx, n, u, pk.q1, pk.scr, st));
-    HIPCHK(poly_binop(POLY_SCALE, pk.q1, nullptr, inv(z0), pk.q1, n - 1, st));
-  }
-  {
-    G1Affine cm;
-    RCCHK(commit(d, prm, pk.q1, n - 1, SRS_G, &cm, st));
-    RCCHK(write_point(cm));
-  }
-  clk.mark("shplonk final");
-  return H2G_OK;
+  MultiopenCtx c = multiopen_ctx();
+  return multiopen_shplonk(c);
 }
 
 // row pieces: the advice transforms run in the permutation stage when every transform of

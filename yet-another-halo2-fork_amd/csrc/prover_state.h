@@ -1,6 +1,6 @@
 // prover_state.h -- what the prover's translation units share (internal: included only by
 // params.cpp, commit.cpp, keygen.cpp, spmd.cpp, prover.cpp, pk_serde.cpp, check_witness.cpp,
-// verifier.cpp, g1_fft.hip):
+// verifier.cpp, g1_fft.hip, and through multiopen.h by multiopen.cpp and kzg.cpp):
 // the params / proving-key / workspace objects, the library's globals and the prototypes of
 // the functions that cross files.  Each global is defined in the file that owns it.
 #pragma once
@@ -66,6 +66,8 @@ struct Params {
   bool has_g2 = false;
   G2Affine g2, s_g2;
   Pool pool;
+  // h2g_multiopen_prove's device scratch (kzg.cpp), made by the first standalone opening
+  std::shared_ptr<void> kzg_ws;
   ~Params() {
     msm_fixed_base_free(&fg);
     msm_fixed_base_free(&fgl);

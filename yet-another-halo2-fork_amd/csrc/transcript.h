@@ -363,6 +363,8 @@ class Transcript {
       : h_("Halo2-Transcript"), kind_(kind), proof_(proof) {
     if (kind_ == TRANSCRIPT_KECCAK256) k_.update("Halo2-Transcript", 16);
   }
+  // where write_point / write_scalar append (a copied transcript object re-points it at its own bytes)
+  void set_sink(std::vector<uint8_t>* proof) { proof_ = proof; }
   void common_scalar(const Fr& s) {
     uint8_t b[33];
     b[0] = 2;

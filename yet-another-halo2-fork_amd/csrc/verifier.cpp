@@ -6,9 +6,8 @@
 //   vanishing verifier               plonk/vanishing/verifier.rs:40-137
 //   permutation verifier             plonk/permutation/verifier.rs:33-253
 //   lookup / shuffle verifiers       plonk/lookup/verifier.rs, plonk/shuffle/verifier.rs
-//   VerifierSHPLONK::verify_proof    poly/kzg/multiopen/shplonk/verifier.rs:45-140
-//   construct_intermediate_sets      poly/kzg/multiopen/shplonk.rs:48-140
-//   VerifierGWC::verify_proof        poly/kzg/multiopen/gwc/verifier.rs:42-123, gwc.rs:25-50
+//   VerifierSHPLONK / VerifierGWC    poly/kzg/multiopen/** -- multiopen.cpp (multiopen_verify_terms), shared
+//                                    with h2g_multiopen_verify below
 //   l_i_range                        poly/domain.rs:425-450
 //   DualMSM::check                   poly/kzg/msm.rs:188-206
 // (oracle/py/verifier.py restates the same sources in Python and is what the tests compare
@@ -24,8 +23,8 @@
 #include <sys/random.h>
 
 #include "msm_seg.h"
+#include "multiopen.h"
 #include "pairing.h"
-#include "prover_state.h"
 
 using namespace h2g;
 using namespace h2g::rt;
@@ -38,8 +37,6 @@ std::map<uint64_t, std::unique_ptr<VerifyingKey>> g_vks;
 }  // namespace h2g
 
 namespace {
-enum { MULTIOPEN_SHPLONK = 0, MULTIOPEN_GWC = 1 };
-constexpr uint32_t BASE_G1 = 0;
 constexpr uint32_t KEY_H = 0xFFFFFFFFu;  // the query key of the h(X) MSM (no single base)
 
 double g_verify_ms[4] = {0, 0, 0, 0};  // host, decompression, MSM, pairing of the last call
@@ -66,21 +63,6 @@ bool fq_below_m(const Fq& a) {
   return br != 0;
 }
 
-struct Term {
-  uint32_t base;
-  Fr s;
-};
-using Msm = std::vector<Term>;
-// equal bases merged (GWC lists a commitment once per opening point)
-void msm_merge(Msm& m) {
-  std::stable_sort(m.begin(), m.end(), [](const Term& a, const Term& b) { return a.base < b.base; });
-  size_t w = 0;
-  for (size_t i = 0; i < m.size(); i++) {
-    if (w && m[w - 1].base == m[i].base) m[w - 1].s = m[w - 1].s + m[i].s;
-    else m[w++] = m[i];
-  }
-  m.resize(w);
-}
 
 // ------------------------------------------------------------------ what the key fixes
 struct Shape {
@@ -152,12 +134,6 @@ int shape_init(Shape& s, const VerifyingKey& vk, int NC, int multiopen, int tran
 }
 
 // ------------------------------------------------------------------ one proof on the host
-struct OpenQuery {
-  uint32_t key;  // the commitment's base index, or KEY_H
-  int rot;       // index into Shape::rots
-  Fr eval;
-};
-
 struct ProofReader {
   const Shape& sh;
   const uint8_t* proof;
@@ -426,7 +402,7 @@ bool proof_terms(const Shape& sh, const h2g_verify_item& it, const G1Affine* pts
 
   // queries, circuit by circuit, then the common ones (verifier.rs:395-470)
   const int r0 = sh.rot_id(0), r_next = sh.rot_id(1), r_prev = sh.rot_id(-1), r_last = sh.rot_id(-(cs.bf + 1));
-  std::vector<OpenQuery> queries;
+  std::vector<VerifierQ> queries;  // key: the commitment's base index, or KEY_H; pt: index into Shape::rots
   for (int c = 0; c < NC; c++) {
     for (size_t qi = 0; qi < cs.adv_q.size(); qi++)
       queries.push_back({adv_cm[c][cs.adv_q[qi].index], sh.rot_id(cs.adv_q[qi].rot), adv_ev[c][qi]});
@@ -454,134 +430,22 @@ bool proof_terms(const Shape& sh, const h2g_verify_item& it, const G1Affine* pts
   queries.push_back({KEY_H, r0, expected_h});
   queries.push_back({random_cm, r0, random_ev});
   for (const auto& q : queries)
-    if (q.rot < 0) return false;  // unreachable: shape_rotations lists every rotation used here
-  std::vector<Fr> point(sh.rots.size());
-  for (size_t i = 0; i < point.size(); i++) point[i] = x * pow_u64(sh.omega, (uint64_t)sh.rots[i]);
-  auto add_obj = [&](Msm& m, uint32_t key, const Fr& f) {  // f * (the commitment or the h MSM)
+    if (q.pt < 0) return false;  // unreachable: shape_rotations lists every rotation used here
+  // the multi-open verifier's scalars (multiopen.cpp), reading this proof's tail points
+  MultiopenVerifyIo io;
+  io.T = &T;
+  io.point.resize(sh.rots.size());
+  for (size_t i = 0; i < io.point.size(); i++) io.point[i] = x * pow_u64(sh.omega, (uint64_t)sh.rots[i]);
+  io.read_point = [&R] { return R.read_point(); };
+  io.ok = [&R] { return R.ok; };
+  io.add_obj = [&h_msm](Msm& m, uint32_t key, const Fr& f) {  // f * (the commitment or the h MSM)
     if (key == KEY_H)
       for (const auto& t : h_msm) m.push_back({t.base, t.s * f});
     else m.push_back({key, f});
   };
+  io.expect_groups = (long)sh.tail_pts;  // GWC: one witness point per distinct rotation
   Msm left, right;
-
-  if (sh.multiopen == MULTIOPEN_GWC) {
-    // VerifierGWC::verify_proof: queries grouped by point in first-appearance order
-    const Fr v = T.squeeze();
-    std::vector<int> group_rot;
-    std::vector<std::vector<const OpenQuery*>> groups;
-    for (const auto& q : queries) {
-      size_t g = 0;
-      while (g < group_rot.size() && group_rot[g] != q.rot) g++;
-      if (g == group_rot.size()) {
-        group_rot.push_back(q.rot);
-        groups.emplace_back();
-      }
-      groups[g].push_back(&q);
-    }
-    if (groups.size() != sh.tail_pts) return false;
-    std::vector<uint32_t> ws(groups.size());
-    for (auto& w : ws) w = R.read_point();
-    const Fr u = T.squeeze();
-    if (!R.ok) return false;
-    Fr eval_multi = Fr::zero(), upow = one;
-    for (size_t g = 0; g < groups.size(); g++) {
-      Fr evb = Fr::zero(), vpow = one;
-      for (const OpenQuery* q : groups[g]) {
-        add_obj(right, q->key, vpow * upow);
-        evb = evb + vpow * q->eval;
-        vpow = vpow * v;
-      }
-      eval_multi = eval_multi + upow * evb;
-      right.push_back({ws[g], upow * point[group_rot[g]]});  // witness_with_aux
-      left.push_back({ws[g], upow});                         // witness
-      upow = upow * u;
-    }
-    right.push_back({BASE_G1, Fr::zero() - eval_multi});
-  } else {
-    // construct_intermediate_sets: commitments in first-appearance order with their point
-    // sets; commitments with equal point sets share a rotation set
-    struct Cm {
-      uint32_t key;
-      std::vector<int> rots;  // sorted
-      std::vector<Fr> evals;  // by rots
-    };
-    std::vector<Cm> cms;
-    for (const auto& q : queries) {
-      size_t i = 0;
-      while (i < cms.size() && cms[i].key != q.key) i++;
-      if (i == cms.size()) cms.push_back({q.key, {}, {}});
-      Cm& cm = cms[i];
-      size_t p = 0;
-      while (p < cm.rots.size() && cm.rots[p] < q.rot) p++;
-      if (p < cm.rots.size() && cm.rots[p] == q.rot) {
-        cm.evals[p] = q.eval;  // the same query twice: the later evaluation (a map in the reference)
-      } else {
-        cm.rots.insert(cm.rots.begin() + p, q.rot);
-        cm.evals.insert(cm.evals.begin() + p, q.eval);
-      }
-    }
-    std::vector<std::vector<int>> set_rots;
-    std::vector<std::vector<const Cm*>> set_cms;
-    for (const auto& cm : cms) {
-      size_t s = 0;
-      while (s < set_rots.size() && set_rots[s] != cm.rots) s++;
-      if (s == set_rots.size()) {
-        set_rots.push_back(cm.rots);
-        set_cms.emplace_back();
-      }
-      set_cms[s].push_back(&cm);
-    }
-    std::vector<int> super;
-    for (const auto& q : queries)
-      if (std::find(super.begin(), super.end(), q.rot) == super.end()) super.push_back(q.rot);
-    const Fr sy = T.squeeze();
-    const Fr v = T.squeeze();
-    const uint32_t h1 = R.read_point();
-    const Fr u = T.squeeze();
-    const uint32_t h2 = R.read_point();
-    if (!R.ok) return false;
-    Fr z0 = Fr::zero(), z0_diff_inv = Fr::zero(), r_outer = Fr::zero(), vpow = one;
-    for (size_t s = 0; s < set_rots.size(); s++) {
-      const std::vector<int>& pts_s = set_rots[s];
-      Fr z_diff = one;
-      for (int p : super)
-        if (std::find(pts_s.begin(), pts_s.end(), p) == pts_s.end()) z_diff = z_diff * (u - point[p]);
-      if (s == 0) {
-        z0 = one;
-        for (int p : pts_s) z0 = z0 * (u - point[p]);
-        z0_diff_inv = inv(z_diff);
-        z_diff = one;
-      } else {
-        z_diff = z_diff * z0_diff_inv;
-      }
-      // the Lagrange basis of this set's points at u (the interpolated r(X) is only used at u)
-      std::vector<Fr> basis(pts_s.size());
-      for (size_t j = 0; j < pts_s.size(); j++) {
-        Fr num = one, den = one;
-        for (size_t k = 0; k < pts_s.size(); k++) {
-          if (k == j) continue;
-          num = num * (u - point[pts_s[k]]);
-          den = den * (point[pts_s[j]] - point[pts_s[k]]);
-        }
-        basis[j] = num * inv(den);
-      }
-      Fr r_inner = Fr::zero(), ypow = one;
-      const Fr scale = vpow * z_diff;
-      for (const Cm* cm : set_cms[s]) {
-        Fr ru = Fr::zero();
-        for (size_t j = 0; j < pts_s.size(); j++) ru = ru + cm->evals[j] * basis[j];
-        r_inner = r_inner + ypow * ru;
-        add_obj(right, cm->key, ypow * scale);
-        ypow = ypow * sy;
-      }
-      r_outer = r_outer + vpow * r_inner * z_diff;
-      vpow = vpow * v;
-    }
-    right.push_back({BASE_G1, Fr::zero() - r_outer});
-    right.push_back({h1, Fr::zero() - z0});
-    right.push_back({h2, u});
-    left.push_back({h2, one});
-  }
+  if (!multiopen_verify_terms(sh.multiopen, queries, io, &left, &right)) return false;
   if (R.pi != sh.pts()) return false;
   msm_merge(left);
   msm_merge(right);
@@ -904,6 +768,94 @@ int h2g_verify_batch(uint64_t vk, const h2g_verifier_params* vp, int multiopen, 
   if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
   if (count == 0) return H2G_OK;
   return verify_impl(d, vk, vp, multiopen, transcript, items, count, rng, true, verdicts, stats);
+}
+
+// Verifier::verify_proof (poly/commitment.rs:171-193) on its own: the caller's commitments and
+// queries, the argument's points read from a read-mode transcript object (decoded on the
+// host, a handful), the scalars of multiopen.cpp, one segmented MSM for (left, right).
+int h2g_multiopen_verify(const h2g_verifier_params* vpp, int scheme, uint64_t transcript, const uint64_t* commitments,
+                         size_t ncommitments, const h2g_verify_query* queries, size_t nqueries, int32_t* verdict,
+                         uint64_t lr[16]) {
+  NEED_DEV_P();
+  if (!verdict) return fail(H2G_ERR_ARG, "multiopen_verify: null argument");
+  *verdict = H2G_VERIFY_MALFORMED;
+  auto ti = g_transcripts.find(transcript);
+  if (ti == g_transcripts.end()) return fail(H2G_ERR_HANDLE, "unknown transcript");
+  TranscriptObj& T = *ti->second;
+  if (scheme != MULTIOPEN_SHPLONK && scheme != MULTIOPEN_GWC)
+    return fail(H2G_ERR_ARG, "multiopen_verify: scheme must be 0 (SHPLONK) or 1 (GWC)");
+  if (!T.read) return fail(H2G_ERR_ARG, "multiopen_verify: a write-mode transcript");
+  if (!commitments || !queries || ncommitments == 0 || nqueries == 0)
+    return fail(H2G_ERR_ARG, "multiopen_verify: no commitments or no queries");
+  if (ncommitments > (1u << 24) || nqueries > (1u << 24)) return fail(H2G_ERR_ARG, "multiopen_verify: too many queries");
+  VerifierPoints vp;
+  RCCHK(load_vp(vpp, &vp));
+  std::vector<G1Affine> bases(1 + ncommitments);
+  bases[BASE_G1] = vp.g1;
+  for (size_t i = 0; i < ncommitments; i++) {
+    G1Affine& c = bases[1 + i];
+    std::memcpy(&c, commitments + 8 * i, sizeof(G1Affine));
+    if (!fq_below_m(c.x) || !fq_below_m(c.y) ||
+        (!c.is_identity() && sqr(c.y) != sqr(c.x) * c.x + from_u64<FqParams>(3)))
+      return fail(H2G_ERR_ARG, "multiopen_verify: commitment " + std::to_string(i) + " is not a point of the curve");
+  }
+  MultiopenVerifyIo io;
+  std::vector<VerifierQ> qs(nqueries);
+  for (size_t i = 0; i < nqueries; i++) {
+    const h2g_verify_query& q = queries[i];
+    if (q.commitment >= ncommitments)
+      return fail(H2G_ERR_ARG, "multiopen_verify: query " + std::to_string(i) + " names an unknown commitment");
+    const Fr pt = fr_from_limbs(q.point), ev = fr_from_limbs(q.eval);
+    if (!fr_below(pt) || !fr_below(ev))
+      return fail(H2G_ERR_ARG, "multiopen_verify: query " + std::to_string(i) + ": value not below r");
+    size_t p = 0;
+    while (p < io.point.size() && !(io.point[p] == pt)) p++;
+    if (p == io.point.size()) io.point.push_back(pt);
+    qs[i] = {1 + q.commitment, (int)p, ev};
+  }
+  bool ok = true;
+  io.T = &T.tr;
+  io.read_point = [&]() -> uint32_t {
+    G1Affine p;
+    if (!ok || !T.read_point(&p)) return ok = false, 0;
+    bases.push_back(p);
+    return (uint32_t)bases.size() - 1;
+  };
+  io.ok = [&ok] { return ok; };
+  io.add_obj = [](Msm& m, uint32_t key, const Fr& f) { m.push_back({key, f}); };
+  Msm left, right;
+  if (!multiopen_verify_terms(scheme, qs, io, &left, &right)) return H2G_OK;  // MALFORMED
+  msm_merge(left);
+  msm_merge(right);
+  std::vector<Fr> scalars;
+  std::vector<uint32_t> index, seg_off(1, 0);
+  for (const Msm* m : {&left, &right}) {
+    for (const auto& t : *m) {
+      index.push_back(t.base);
+      scalars.push_back(t.s);
+    }
+    seg_off.push_back((uint32_t)index.size());
+  }
+  hipStream_t st = d->stream;
+  DevMem d_bases, d_sc, d_ix, d_off, d_lr;
+  StreamSyncGuard guard{st};
+  HIPCHK(hipMalloc(&d_bases.p, bases.size() * sizeof(G1Affine)));
+  HIPCHK(hipMalloc(&d_sc.p, scalars.size() * sizeof(Fr)));
+  HIPCHK(hipMalloc(&d_ix.p, index.size() * 4));
+  HIPCHK(hipMalloc(&d_off.p, seg_off.size() * 4));
+  HIPCHK(hipMalloc(&d_lr.p, 2 * sizeof(G1Affine)));
+  HIPCHK(hipMemcpyAsync(d_bases.p, bases.data(), bases.size() * sizeof(G1Affine), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_sc.p, scalars.data(), scalars.size() * sizeof(Fr), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_ix.p, index.data(), index.size() * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_off.p, seg_off.data(), seg_off.size() * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(msm_segmented((const G1Affine*)d_bases.p, bases.size(), (const Fr*)d_sc.p, (const uint32_t*)d_ix.p,
+                       (const uint32_t*)d_off.p, 2, (G1Affine*)d_lr.p, st));
+  G1Affine out[2];
+  HIPCHK(hipMemcpyAsync(out, d_lr.p, sizeof(out), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (lr) std::memcpy(lr, out, sizeof(out));
+  *verdict = dual_check(vp, out[0], out[1]) ? H2G_VERIFY_OK : H2G_VERIFY_REJECTED;
+  return H2G_OK;
 }
 
 /* wall milliseconds of the last h2g_verify_proof / h2g_verify_batch: [0] host (transcripts,

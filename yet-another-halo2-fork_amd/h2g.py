@@ -151,6 +151,28 @@ _SIGS = {
     "h2g_verify_proof": ([U64, VP, I32, I32, VP, ctypes.POINTER(ctypes.c_int32)], I32),
     "h2g_verify_batch": ([U64, VP, I32, I32, VP, SZ, VP, ctypes.POINTER(ctypes.c_int32), U64P], I32),
     "h2g_verify_stages": ([ctypes.POINTER(ctypes.c_double)], I32),
+    "h2g_transcript_new_write": ([I32, ctypes.POINTER(U64)], I32),
+    "h2g_transcript_new_read": ([I32, ctypes.c_char_p, SZ, ctypes.POINTER(U64)], I32),
+    "h2g_transcript_common_point": ([U64, U64P], I32),
+    "h2g_transcript_common_scalar": ([U64, U64P], I32),
+    "h2g_transcript_write_point": ([U64, U64P], I32),
+    "h2g_transcript_write_scalar": ([U64, U64P], I32),
+    "h2g_transcript_read_point": ([U64, U64P], I32),
+    "h2g_transcript_read_scalar": ([U64, U64P], I32),
+    "h2g_transcript_squeeze": ([U64, U64P], I32),
+    "h2g_transcript_bytes": ([U64, VP, SZ, ctypes.POINTER(SZ)], I32),
+    "h2g_transcript_remaining": ([U64, ctypes.POINTER(SZ)], I32),
+    "h2g_transcript_free": ([U64], I32),
+    "h2g_params_commit": ([U64, U64P, SZ, U64P, ctypes.POINTER(I32)], I32),
+    "h2g_params_commit_lagrange": ([U64, U64P, SZ, U64P, ctypes.POINTER(I32)], I32),
+    "h2g_params_commit_dev": ([U64, VP, SZ, U64P, ctypes.POINTER(I32), VP], I32),
+    "h2g_params_commit_lagrange_dev": ([U64, VP, SZ, U64P, ctypes.POINTER(I32), VP], I32),
+    "h2g_fr_eval": ([U64P, SZ, U64P, U64P], I32),
+    "h2g_fr_eval_dev": ([VP, SZ, U64P, U64P, VP], I32),
+    "h2g_kate_division": ([U64P, SZ, U64P, U64P], I32),
+    "h2g_kate_division_dev": ([VP, SZ, U64P, VP, VP], I32),
+    "h2g_multiopen_prove": ([U64, I32, U64, VP, SZ, VP, SZ], I32),
+    "h2g_multiopen_verify": ([VP, I32, U64, U64P, SZ, VP, SZ, ctypes.POINTER(ctypes.c_int32), U64P], I32),
 }
 
 TRANSCRIPTS = {"blake2b": 0, "keccak256": 1}  # Blake2bWrite / Keccak256Write (h2g_pk_set_transcript)
@@ -754,6 +776,16 @@ class Params:
         check(lib().h2g_params_verifier(self.handle, ctypes.byref(vp)))
         return vp
 
+    # the polynomial-commitment layer on its own (bodies below, beside Transcript)
+    def commit(self, coeffs, dev_len=None, stream=None):
+        return _params_commit(self, coeffs, dev_len, stream)
+
+    def commit_lagrange(self, evals, dev_len=None, stream=None):
+        return _params_commit_lagrange(self, evals, dev_len, stream)
+
+    def multiopen_prove(self, transcript, polys, queries, scheme="shplonk"):
+        return _params_multiopen_prove(self, transcript, polys, queries, scheme)
+
     def set_slab(self, lo, hi):
         """fixed-base windows for this rank's point slab [lo, hi) (one proof over several GPUs)"""
         check(lib().h2g_params_set_slab(self.handle, lo, hi))
@@ -1108,6 +1140,179 @@ def verify_stages():
     ms = (ctypes.c_double * 4)()
     check(lib().h2g_verify_stages(ms))
     return tuple(ms)
+
+
+# ----------------------------------------------------------------------------- the KZG layer on its own
+MULTIOPEN = {"shplonk": 0, "gwc": 1}
+
+
+class Transcript:
+    """A transcript object of the library: Blake2bWrite / Keccak256Write (proof=None) or
+    Blake2bRead / Keccak256Read over `proof` (transcript.rs:291-463).  Host only.  Points are
+    (8,) uint64 affine Montgomery limbs, scalars and challenges (4,) uint64 Montgomery limbs."""
+
+    def __init__(self, kind="blake2b", proof=None):
+        h = U64()
+        if proof is None:
+            check(lib().h2g_transcript_new_write(TRANSCRIPTS[kind], ctypes.byref(h)))
+        else:
+            check(lib().h2g_transcript_new_read(TRANSCRIPTS[kind], bytes(proof), len(proof), ctypes.byref(h)))
+        self.handle = h.value
+        self.kind = kind
+
+    def common_point(self, p):
+        check(lib().h2g_transcript_common_point(self.handle, p64(np.ascontiguousarray(p, dtype=np.uint64))))
+
+    def common_scalar(self, s):
+        check(lib().h2g_transcript_common_scalar(self.handle, p64(np.ascontiguousarray(s, dtype=np.uint64))))
+
+    def write_point(self, p):
+        check(lib().h2g_transcript_write_point(self.handle, p64(np.ascontiguousarray(p, dtype=np.uint64))))
+
+    def write_scalar(self, s):
+        check(lib().h2g_transcript_write_scalar(self.handle, p64(np.ascontiguousarray(s, dtype=np.uint64))))
+
+    def read_point(self):
+        out = np.zeros(8, dtype=np.uint64)
+        check(lib().h2g_transcript_read_point(self.handle, p64(out)))
+        return out
+
+    def read_scalar(self):
+        out = np.zeros(4, dtype=np.uint64)
+        check(lib().h2g_transcript_read_scalar(self.handle, p64(out)))
+        return out
+
+    def squeeze(self):
+        out = np.zeros(4, dtype=np.uint64)
+        check(lib().h2g_transcript_squeeze(self.handle, p64(out)))
+        return out
+
+    def bytes(self):
+        """finalize(): the bytes written so far (write mode)"""
+        n = SZ()
+        check(lib().h2g_transcript_bytes(self.handle, None, 0, ctypes.byref(n)))
+        buf = ctypes.create_string_buffer(max(n.value, 1))
+        check(lib().h2g_transcript_bytes(self.handle, ctypes.cast(buf, VP), n.value, ctypes.byref(n)))
+        return buf.raw[: n.value]
+
+    def remaining(self):
+        n = SZ()
+        check(lib().h2g_transcript_remaining(self.handle, ctypes.byref(n)))
+        return n.value
+
+    def close(self):
+        if self.handle:
+            lib().h2g_transcript_free(self.handle)
+            self.handle = 0
+
+
+class PolyRef(ctypes.Structure):
+    """h2g_poly_ref"""
+    _fields_ = [("coeffs", VP), ("len", SZ), ("on_device", I32)]
+
+
+class OpenQuery(ctypes.Structure):
+    """h2g_open_query"""
+    _fields_ = [("poly", U32), ("reserved", U32), ("point", U64 * 4)]
+
+
+class VerifyQuery(ctypes.Structure):
+    """h2g_verify_query"""
+    _fields_ = [("commitment", U32), ("reserved", U32), ("point", U64 * 4), ("eval", U64 * 4)]
+
+
+def _limbs4(v):
+    a = np.ascontiguousarray(v, dtype=np.uint64).reshape(4)
+    return (U64 * 4)(*[int(t) for t in a])
+
+
+def _commit(fn_host, fn_dev, handle, vals, dev_len, stream):
+    out = np.zeros(8, dtype=np.uint64)
+    ident = I32(0)
+    if dev_len is not None:  # vals is a device pointer
+        check(fn_dev(handle, VP(vals), dev_len, p64(out), ctypes.byref(ident), VP(stream) if stream else None))
+    else:
+        a = np.ascontiguousarray(vals, dtype=np.uint64).reshape(-1, 4)
+        check(fn_host(handle, p64(a) if a.size else None, len(a), p64(out), ctypes.byref(ident)))
+    return out
+
+
+def _params_commit(self, coeffs, dev_len=None, stream=None):
+    """ParamsKZG::commit (kzg/commitment.rs:354-366) -> (8,) affine (identity = zeros).  coeffs:
+    (len, 4) Montgomery limbs, or a device pointer with dev_len"""
+    return _commit(lib().h2g_params_commit, lib().h2g_params_commit_dev, self.handle, coeffs, dev_len, stream)
+
+
+def _params_commit_lagrange(self, evals, dev_len=None, stream=None):
+    """ParamsKZG::commit_lagrange (kzg/commitment.rs:305-317)"""
+    return _commit(lib().h2g_params_commit_lagrange, lib().h2g_params_commit_lagrange_dev, self.handle, evals,
+                   dev_len, stream)
+
+
+def _params_multiopen_prove(self, transcript, polys, queries, scheme="shplonk"):
+    """Prover::create_proof (poly/commitment.rs:141-168) into `transcript` (write mode).  polys:
+    (len, 4) uint64 arrays (host) or (device pointer, len) tuples; queries: (poly index, point)
+    with point (4,) Montgomery limbs, in the argument's order."""
+    keep = []
+    refs = (PolyRef * max(len(polys), 1))()
+    for i, p in enumerate(polys):
+        if isinstance(p, tuple):
+            refs[i].coeffs, refs[i].len, refs[i].on_device = p[0], p[1], 1
+        else:
+            a = np.ascontiguousarray(p, dtype=np.uint64).reshape(-1, 4)
+            keep.append(a)
+            refs[i].coeffs, refs[i].len, refs[i].on_device = (a.ctypes.data if a.size else None), len(a), 0
+    qs = (OpenQuery * max(len(queries), 1))()
+    for i, (poly, pt) in enumerate(queries):
+        qs[i].poly = poly
+        qs[i].point = _limbs4(pt)
+    check(lib().h2g_multiopen_prove(self.handle, MULTIOPEN[scheme], transcript.handle, refs, len(polys), qs,
+                                    len(queries)))
+    del keep
+
+
+def multiopen_verify(vp, transcript, commitments, queries, scheme="shplonk"):
+    """Verifier::verify_proof + DualMSM::check (h2g_multiopen_verify) -> (verdict, lr).
+    commitments: (m, 8) affine; queries: (commitment index, point, eval); lr: (2, 8) affine
+    (left, right) of the DualMSM, None for a malformed argument."""
+    cm = np.ascontiguousarray(commitments, dtype=np.uint64).reshape(-1, 8)
+    qs = (VerifyQuery * max(len(queries), 1))()
+    for i, (c, pt, ev) in enumerate(queries):
+        qs[i].commitment = c
+        qs[i].point = _limbs4(pt)
+        qs[i].eval = _limbs4(ev)
+    verdict = ctypes.c_int32(-2)
+    lr = np.zeros((2, 8), dtype=np.uint64)
+    check(lib().h2g_multiopen_verify(ctypes.byref(vp), MULTIOPEN[scheme], transcript.handle,
+                                     p64(cm) if cm.size else None, len(cm), qs, len(queries),
+                                     ctypes.byref(verdict), p64(lr)))
+    return verdict.value, (lr if verdict.value != VERIFY_MALFORMED else None)
+
+
+def fr_eval(poly, x, dev_len=None, stream=None):
+    """eval_polynomial (arithmetic.rs:57-82).  poly: (len, 4) limbs, or a device pointer with dev_len"""
+    out = np.zeros(4, dtype=np.uint64)
+    xs = np.ascontiguousarray(x, dtype=np.uint64)
+    if dev_len is not None:
+        check(lib().h2g_fr_eval_dev(VP(poly), dev_len, p64(xs), p64(out), VP(stream) if stream else None))
+    else:
+        a = np.ascontiguousarray(poly, dtype=np.uint64).reshape(-1, 4)
+        check(lib().h2g_fr_eval(p64(a) if a.size else None, len(a), p64(xs), p64(out)))
+    return out
+
+
+def kate_division(a, b):
+    """kate_division (arithmetic.rs:101-120): (len, 4) -> (len - 1, 4)"""
+    a = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 4)
+    q = np.zeros((max(len(a) - 1, 0), 4), dtype=np.uint64)
+    check(lib().h2g_kate_division(p64(a) if a.size else None, len(a), p64(np.ascontiguousarray(b, dtype=np.uint64)),
+                                  p64(q) if q.size else None))
+    return q
+
+
+def kate_division_dev(d_a, n, b, d_q, stream=None):
+    check(lib().h2g_kate_division_dev(VP(d_a), n, p64(np.ascontiguousarray(b, dtype=np.uint64)), VP(d_q),
+                                      VP(stream) if stream else None))
 
 
 def msm_segmented(bases, scalars, seg_off, index=None):
