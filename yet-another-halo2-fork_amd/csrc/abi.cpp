@@ -48,13 +48,22 @@ int prof_entries_slot(MsmPhaseEvents* ev) {
   if (ev->entries) *ev->entries = 0;
   return H2G_OK;
 }
+// a profiled MSM's phase events and entry-count slot; *pe stays null with profiling off
+static int prof_begin(int msms, MsmPhaseEvents** pe) {
+  *pe = nullptr;
+  if (!g_profile) return H2G_OK;
+  MsmPhaseEvents ev;
+  for (auto& e : ev.ev) HIPCHK(hipEventCreate(&e));
+  RCCHK(prof_entries_slot(&ev));
+  ev.msms = msms;
+  g_msm_prof.push_back(ev);
+  *pe = &g_msm_prof.back();
+  return H2G_OK;
+}
 int g_cur = 0;
 std::map<uint64_t, Descriptor> g_desc;
 std::map<uint64_t, std::unique_ptr<Domain>> g_dom;
 uint64_t g_next_handle = 1;
-
-
-
 
 int fail(int code, const std::string& msg) {
   g_err = msg;
@@ -64,26 +73,10 @@ int hip_fail(hipError_t e, const char* what) {
   return fail(H2G_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
 }
 
-
-
-
-
-
-
-
-
-
-
-
-
-
-
 Device* cur() {
   if (g_devs.empty()) return nullptr;
   return g_devs[g_cur].get();
 }
-
-
 
 Fr fr_from_limbs(const uint64_t* v) {
   Fr r;
@@ -106,7 +99,6 @@ Fr zeta() {
   const uint64_t v[4] = {0x93e7cede4a0329b3ULL, 0x7d4fdca77a96c167ULL, 0x8be4ba08b19a750aULL, 0x1cbd5653a5661c25ULL};
   return fr_from_limbs(v);
 }
-
 
 int get_tables(Device* d, const Fr& omega, int L, hipStream_t st, NttTables* out, const Fr& fold) {
   NttKey key{L, {}, {}};
@@ -136,31 +128,16 @@ int msm_dev_impl(Device* d, const void* sc, const void* bs, size_t n, int c, voi
   if (n > 0x7fffffffULL) return fail(H2G_ERR_ARG, "msm: n too large");
   MsmConfig cfg;
   cfg.c = c;
-  MsmPhaseEvents* pe = nullptr;
-  if (g_profile) {
-    MsmPhaseEvents ev;
-    for (auto& e : ev.ev) HIPCHK(hipEventCreate(&e));
-    RCCHK(prof_entries_slot(&ev));
-    g_msm_prof.push_back(ev);
-    pe = &g_msm_prof.back();
-  }
+  MsmPhaseEvents* pe;
+  RCCHK(prof_begin(1, &pe));
   HIPCHK(msm_run(reinterpret_cast<const Fr*>(sc), reinterpret_cast<const G1Affine*>(bs), n, &d->msm, cfg,
                  reinterpret_cast<G1Affine*>(out), st, pe));
   return H2G_OK;
 }
 
-// Host-returning MSM: device phases, then the W window sums (W x 128 B) come back
-// to the host and are combined there (msm_windows_host_finish); synchronous.
-int msm_host_impl(Device* d, const void* sc, const void* bs, size_t n, int c, uint64_t* out, int* is_id,
-                  hipStream_t st) {
-  if (n == 0) {
-    std::memset(out, 0, 64);
-    if (is_id) *is_id = 1;
-    return H2G_OK;
-  }
-  int rc = msm_dev_impl(d, sc, bs, n, c, nullptr, st);
-  if (rc) return rc;
-  const int W = d->msm.last_W;
+// the first W window sums of d->msm come back to the host and are combined there
+// (msm_windows_host_finish): the affine result, and whether it is the identity
+static int msm_windows_to_host(Device* d, int W, uint64_t* out, int* is_id, hipStream_t st) {
   if (!d->h_windows) HIPCHK(hipHostMalloc(&d->h_windows, 256 * sizeof(G1xyzz), hipHostMallocDefault));
   HIPCHK(hipMemcpyAsync(d->h_windows, d->msm.windows, (size_t)W * sizeof(G1xyzz), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
@@ -174,6 +151,20 @@ int msm_host_impl(Device* d, const void* sc, const void* bs, size_t n, int c, ui
   return H2G_OK;
 }
 
+// Host-returning MSM: device phases, then the W window sums (W x 128 B) come back
+// to the host (msm_windows_to_host); synchronous.
+int msm_host_impl(Device* d, const void* sc, const void* bs, size_t n, int c, uint64_t* out, int* is_id,
+                  hipStream_t st) {
+  if (n == 0) {
+    std::memset(out, 0, 64);
+    if (is_id) *is_id = 1;
+    return H2G_OK;
+  }
+  int rc = msm_dev_impl(d, sc, bs, n, c, nullptr, st);
+  if (rc) return rc;
+  return msm_windows_to_host(d, d->msm.last_W, out, is_id, st);
+}
+
 int msm_fixed_host_impl(Device* d, const void* sc, const MsmFixedBase& fb, size_t off, size_t n, uint64_t* out,
                         int* is_id, hipStream_t st) {
   if (n == 0) {
@@ -181,26 +172,10 @@ int msm_fixed_host_impl(Device* d, const void* sc, const MsmFixedBase& fb, size_
     if (is_id) *is_id = 1;
     return H2G_OK;
   }
-  MsmPhaseEvents* pe = nullptr;
-  if (g_profile) {
-    MsmPhaseEvents ev;
-    for (auto& e : ev.ev) HIPCHK(hipEventCreate(&e));
-    RCCHK(prof_entries_slot(&ev));
-    g_msm_prof.push_back(ev);
-    pe = &g_msm_prof.back();
-  }
+  MsmPhaseEvents* pe;
+  RCCHK(prof_begin(1, &pe));
   HIPCHK(msm_run_fixed(reinterpret_cast<const Fr*>(sc), fb, off, n, &d->msm, nullptr, st, pe));
-  if (!d->h_windows) HIPCHK(hipHostMalloc(&d->h_windows, 256 * sizeof(G1xyzz), hipHostMallocDefault));
-  HIPCHK(hipMemcpyAsync(d->h_windows, d->msm.windows, sizeof(G1xyzz), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  const G1Affine r = msm_windows_host_finish(reinterpret_cast<const G1xyzz*>(d->h_windows), 1, d->msm.last_c);
-  std::memcpy(out, &r, 64);
-  if (is_id) {
-    uint64_t x = 0;
-    for (int i = 0; i < 8; i++) x |= out[i];
-    *is_id = x == 0;
-  }
-  return H2G_OK;
+  return msm_windows_to_host(d, 1, out, is_id, st);
 }
 
 // the asynchronous MSMs' streams, result ring and events (h2g_init creates them, right
@@ -235,14 +210,7 @@ int msm_fixed_launch_batch(Device* d, const void* const* sc, int nb, const MsmFi
   HIPCHK(hipEventRecord(d->ring_ev[rings[0]], producer));
   HIPCHK(hipStreamWaitEvent(ms, d->ring_ev[rings[0]], 0));
   MsmPhaseEvents* pe = nullptr;
-  if (g_profile && n > 0) {
-    MsmPhaseEvents ev;
-    for (auto& e : ev.ev) HIPCHK(hipEventCreate(&e));
-    RCCHK(prof_entries_slot(&ev));
-    ev.msms = nb;
-    g_msm_prof.push_back(ev);
-    pe = &g_msm_prof.back();
-  }
+  if (n > 0) RCCHK(prof_begin(nb, &pe));
   G1xyzz* host = reinterpret_cast<G1xyzz*>(d->h_ring);
   if (n == 0) {
     for (int b = 0; b < nb; b++) std::memset(host + rings[b], 0, sizeof(G1xyzz));  // identity (ZZ = 0)
@@ -360,7 +328,10 @@ Domain* get_dom(uint64_t h) {
   auto it = g_dom.find(h);
   return it == g_dom.end() ? nullptr : it->second.get();
 }
-
+Descriptor* find_desc(uint64_t h) {
+  auto it = g_desc.find(h);
+  return it == g_desc.end() ? nullptr : &it->second;
+}
 
 int domain_init(Domain* dm, uint32_t j, uint32_t k) {   // EvaluationDomain::new (domain.rs:38-144)
   if (j < 2 || k > FR_S) return fail(H2G_ERR_ARG, "domain: bad j/k");
@@ -393,14 +364,9 @@ int domain_init(Domain* dm, uint32_t j, uint32_t k) {   // EvaluationDomain::new
   dm->bary = inv(from_u64<FrParams>(n));
   dm->ext_omega_inv = inv(eo);
   dm->omega_inv = inv(o);
-  HIPCHK(hipMalloc(&dm->d_t, tlen * sizeof(Fr)));
-  HIPCHK(hipMemcpy(dm->d_t, dm->t_evals.data(), tlen * sizeof(Fr), hipMemcpyHostToDevice));
+  HIPCHK(dm->d_t.ensure(tlen));
+  HIPCHK(hipMemcpy(dm->d_t.p, dm->t_evals.data(), tlen * sizeof(Fr), hipMemcpyHostToDevice));
   return H2G_OK;
-}
-
-void domain_release(Domain* dm) {
-  if (dm->d_t) (void)hipFree(dm->d_t);
-  dm->d_t = nullptr;
 }
 
 // lagrange_to_coeff (domain.rs:216-226): iFFT, * 1/n
@@ -454,6 +420,25 @@ Fr fr_delta() {
   if (!d) return fail(H2G_ERR_STATE, "h2g_init has not been called");         \
   HIPCHK(hipSetDevice(d->id));
 
+// The host-pointer wrappers' round trip: `in` goes up, fn(d_in, d_out) runs the device-pointer
+// entry point on the library stream, `out` comes back; in place, d_out is d_in
+template <class F>
+static int host_roundtrip(size_t in_elems, const uint64_t* in, size_t out_elems, uint64_t* out, bool in_place, F&& fn) {
+  NEED_DEV();
+  DevBuf& dout = in_place ? d->b : d->c;
+  HIPCHK(d->b.ensure(in_elems * 32 + 32));
+  HIPCHK(dout.ensure(out_elems * 32 + 32));
+  HIPCHK(hipMemcpyAsync(d->b.p, in, in_elems * 32, hipMemcpyHostToDevice, d->stream));
+  RCCHK(fn((void*)d->b.p, (void*)dout.p));
+  HIPCHK(hipMemcpyAsync(out, dout.p, out_elems * 32, hipMemcpyDeviceToHost, d->stream));
+  HIPCHK(hipStreamSynchronize(d->stream));
+  return H2G_OK;
+}
+template <class F>
+static int host_in_place(size_t elems, uint64_t* a, F&& fn) {
+  return host_roundtrip(elems, a, elems, a, true, [&](void* da, void*) { return fn(da); });
+}
+
 extern "C" {
 
 int h2g_abi_version(void) { return 1; }
@@ -496,13 +481,7 @@ int h2g_init(const int* devices, int ndev) {
 
 int h2g_shutdown(void) {
   std::lock_guard<std::recursive_mutex> lk(g_mu);
-  for (auto& kv : g_desc) {
-    if (kv.second.d) (void)hipFree(kv.second.d);
-  }
   g_desc.clear();
-  for (auto& kv : g_dom) {
-    if (kv.second->d_t) (void)hipFree(kv.second->d_t);
-  }
   g_dom.clear();
   for (auto& dev : g_devs) {
     (void)hipSetDevice(dev->id);
@@ -580,18 +559,19 @@ static int make_desc(const uint64_t* data, size_t n, size_t elem_bytes, bool is_
   ds.device = g_cur;
   ds.n = n;
   ds.is_base = is_base;
-  HIPCHK(hipMalloc(&ds.d, n * elem_bytes + 64));
-  HIPCHK(hipMemcpyAsync(ds.d, data, n * elem_bytes, hipMemcpyHostToDevice, d->stream));
+  HIPCHK(ds.mem.ensure(n * elem_bytes + 64));
+  HIPCHK(hipMemcpyAsync(ds.mem.p, data, n * elem_bytes, hipMemcpyHostToDevice, d->stream));
+  ds.d = ds.mem.p;
   if (is_base && n >= 2) {
     // resident bases: precompute the fixed-base windows; the table's window 0 is the bases
-    HIPCHK(msm_fixed_base_build((const G1Affine*)ds.d, n, 0, &ds.fb, d->stream));
+    HIPCHK(msm_fixed_base_build((const G1Affine*)ds.mem.p, n, 0, &ds.fb, d->stream));
     HIPCHK(hipStreamSynchronize(d->stream));
-    (void)hipFree(ds.d);
+    ds.mem.release();
     ds.d = ds.fb.table;
   }
   HIPCHK(hipStreamSynchronize(d->stream));
   *handle = g_next_handle++;
-  g_desc[*handle] = ds;
+  g_desc.emplace(*handle, std::move(ds));
   return H2G_OK;
 }
 
@@ -612,69 +592,66 @@ int h2g_msm_base_descriptor_dev(const void* d_bases, size_t n, int window_bits, 
   HIPCHK(hipStreamSynchronize(d->stream));
   ds.d = ds.fb.table;
   *handle = g_next_handle++;
-  g_desc[*handle] = ds;
+  g_desc.emplace(*handle, std::move(ds));
   return H2G_OK;
 }
 
 int h2g_msm_with_cached_base_dev(const void* d_scalars, size_t n, uint64_t base, size_t off, uint64_t out[8],
                                  int* is_id, void* stream) {
   NEED_DEV();
-  auto it = g_desc.find(base);
-  if (it == g_desc.end() || !it->second.is_base) return fail(H2G_ERR_HANDLE, "unknown base descriptor");
-  if (off + n > it->second.n) return fail(H2G_ERR_ARG, "msm: bases.len() < size");
+  Descriptor* it = find_desc(base);
+  if (!it || !it->is_base) return fail(H2G_ERR_HANDLE, "unknown base descriptor");
+  if (off + n > it->n) return fail(H2G_ERR_ARG, "msm: bases.len() < size");
   if (n && !d_scalars) return fail(H2G_ERR_ARG, "msm: null scalars");
-  return msm_desc_impl(d, d_scalars, it->second, off, n, out, is_id, pick_stream(d, stream));
+  return msm_desc_impl(d, d_scalars, *it, off, n, out, is_id, pick_stream(d, stream));
 }
 
 int h2g_msm_descriptor_free(uint64_t handle) {
   std::lock_guard<std::recursive_mutex> lk(g_mu);
-  auto it = g_desc.find(handle);
-  if (it == g_desc.end()) return fail(H2G_ERR_HANDLE, "unknown descriptor");
-  if (it->second.d) (void)hipFree(it->second.d);
-  g_desc.erase(it);
+  if (!g_desc.erase(handle)) return fail(H2G_ERR_HANDLE, "unknown descriptor");
   return H2G_OK;
 }
 int h2g_descriptor_device_ptr(uint64_t handle, void** d_ptr, size_t* n) {
   std::lock_guard<std::recursive_mutex> lk(g_mu);
-  auto it = g_desc.find(handle);
-  if (it == g_desc.end()) return fail(H2G_ERR_HANDLE, "unknown descriptor");
-  if (d_ptr) *d_ptr = it->second.d;
-  if (n) *n = it->second.n;
+  Descriptor* it = find_desc(handle);
+  if (!it) return fail(H2G_ERR_HANDLE, "unknown descriptor");
+  if (d_ptr) *d_ptr = it->d;
+  if (n) *n = it->n;
   return H2G_OK;
 }
 
 int h2g_msm_with_cached_scalars(uint64_t coeffs, const uint64_t* bases, size_t n, uint64_t out[8], int* is_id) {
   NEED_DEV();
-  auto it = g_desc.find(coeffs);
-  if (it == g_desc.end() || it->second.is_base) return fail(H2G_ERR_HANDLE, "unknown coeffs descriptor");
-  if (it->second.n != n) return fail(H2G_ERR_ARG, "msm: coeffs.len() != bases.len()");
+  Descriptor* it = find_desc(coeffs);
+  if (!it || it->is_base) return fail(H2G_ERR_HANDLE, "unknown coeffs descriptor");
+  if (it->n != n) return fail(H2G_ERR_ARG, "msm: coeffs.len() != bases.len()");
   HIPCHK(d->b.ensure(n * 64 + 64));
   HIPCHK(d->out.ensure(64));
   HIPCHK(hipMemcpyAsync(d->b.p, bases, n * 64, hipMemcpyHostToDevice, d->stream));
-  return msm_host_impl(d, it->second.d, d->b.p, n, 0, out, is_id, d->stream);
+  return msm_host_impl(d, it->d, d->b.p, n, 0, out, is_id, d->stream);
 }
 
 int h2g_msm_with_cached_base(const uint64_t* coeffs, size_t n, uint64_t base, size_t off, uint64_t out[8],
                              int* is_id) {
   NEED_DEV();
-  auto it = g_desc.find(base);
-  if (it == g_desc.end() || !it->second.is_base) return fail(H2G_ERR_HANDLE, "unknown base descriptor");
-  if (off + n > it->second.n) return fail(H2G_ERR_ARG, "msm: bases.len() < size");
+  Descriptor* it = find_desc(base);
+  if (!it || !it->is_base) return fail(H2G_ERR_HANDLE, "unknown base descriptor");
+  if (off + n > it->n) return fail(H2G_ERR_ARG, "msm: bases.len() < size");
   HIPCHK(d->a.ensure(n * 32 + 32));
   HIPCHK(d->out.ensure(64));
   HIPCHK(hipMemcpyAsync(d->a.p, coeffs, n * 32, hipMemcpyHostToDevice, d->stream));
-  return msm_desc_impl(d, d->a.p, it->second, off, n, out, is_id, d->stream);
+  return msm_desc_impl(d, d->a.p, *it, off, n, out, is_id, d->stream);
 }
 
 int h2g_msm_with_cached_inputs(uint64_t coeffs, uint64_t base, size_t off, uint64_t out[8], int* is_id) {
   NEED_DEV();
-  auto ic = g_desc.find(coeffs);
-  auto ib = g_desc.find(base);
-  if (ic == g_desc.end() || ic->second.is_base) return fail(H2G_ERR_HANDLE, "unknown coeffs descriptor");
-  if (ib == g_desc.end() || !ib->second.is_base) return fail(H2G_ERR_HANDLE, "unknown base descriptor");
-  const size_t n = ic->second.n;
-  if (off + n > ib->second.n) return fail(H2G_ERR_ARG, "msm: bases.len() < size");
-  return msm_desc_impl(d, ic->second.d, ib->second, off, n, out, is_id, d->stream);
+  Descriptor* ic = find_desc(coeffs);
+  Descriptor* ib = find_desc(base);
+  if (!ic || ic->is_base) return fail(H2G_ERR_HANDLE, "unknown coeffs descriptor");
+  if (!ib || !ib->is_base) return fail(H2G_ERR_HANDLE, "unknown base descriptor");
+  const size_t n = ic->n;
+  if (off + n > ib->n) return fail(H2G_ERR_ARG, "msm: bases.len() < size");
+  return msm_desc_impl(d, ic->d, *ib, off, n, out, is_id, d->stream);
 }
 
 int h2g_msm_dev(const void* sc, const void* bs, size_t n, void* out, void* stream) {
@@ -716,14 +693,7 @@ int h2g_fft_dev(void* a, uint32_t log_n, const uint64_t omega[4], void* stream) 
 int h2g_fft(uint64_t* a, uint32_t log_n, const uint64_t omega[4]) {
   NEED_DEV();
   if (!a || !omega || log_n > FR_S) return fail(H2G_ERR_ARG, "fft: bad argument");
-  const size_t bytes = ((size_t)1 << log_n) * 32;
-  HIPCHK(d->a.ensure(bytes));
-  HIPCHK(hipMemcpyAsync(d->a.p, a, bytes, hipMemcpyHostToDevice, d->stream));
-  int rc = h2g_fft_dev(d->a.p, log_n, omega, nullptr);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(a, d->a.p, bytes, hipMemcpyDeviceToHost, d->stream));
-  HIPCHK(hipStreamSynchronize(d->stream));
-  return H2G_OK;
+  return host_in_place((size_t)1 << log_n, a, [&](void* da) { return h2g_fft_dev(da, log_n, omega, nullptr); });
 }
 
 // ---------------------------------------------------------------- EvaluationDomain
@@ -739,10 +709,7 @@ int h2g_domain_create(uint32_t j, uint32_t k, uint64_t* handle) {
 
 int h2g_domain_free(uint64_t handle) {
   std::lock_guard<std::recursive_mutex> lk(g_mu);
-  auto it = g_dom.find(handle);
-  if (it == g_dom.end()) return fail(H2G_ERR_HANDLE, "unknown domain");
-  if (it->second->d_t) (void)hipFree(it->second->d_t);
-  g_dom.erase(it);
+  if (!g_dom.erase(handle)) return fail(H2G_ERR_HANDLE, "unknown domain");
   return H2G_OK;
 }
 
@@ -790,70 +757,39 @@ int h2g_divide_by_vanishing_poly_dev(uint64_t dom, void* a, void* stream) {
   Domain* dm = get_dom(dom);
   if (!dm) return fail(H2G_ERR_HANDLE, "unknown domain");
   if (!a) return fail(H2G_ERR_ARG, "null");
-  HIPCHK(poly_mul_cyclic((Fr*)a, 1ull << dm->ek, dm->d_t, dm->t_evals.size(), pick_stream(d, stream)));
+  HIPCHK(poly_mul_cyclic((Fr*)a, 1ull << dm->ek, dm->d_t.p, dm->t_evals.size(), pick_stream(d, stream)));
   return H2G_OK;
 }
 
 // host-pointer domain wrappers
-static int host_roundtrip(size_t in_elems, const uint64_t* in, size_t out_elems, uint64_t* out,
-                          int (*fn)(uint64_t, const void*, void*, void*), uint64_t dom) {
-  NEED_DEV();
-  HIPCHK(d->b.ensure(in_elems * 32 + 32));
-  HIPCHK(d->c.ensure(out_elems * 32 + 32));
-  HIPCHK(hipMemcpyAsync(d->b.p, in, in_elems * 32, hipMemcpyHostToDevice, d->stream));
-  int rc = fn(dom, d->b.p, d->c.p, nullptr);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(out, d->c.p, out_elems * 32, hipMemcpyDeviceToHost, d->stream));
-  HIPCHK(hipStreamSynchronize(d->stream));
-  return H2G_OK;
-}
-
 int h2g_lagrange_to_coeff(uint64_t dom, uint64_t* a) {
   NEED_DEV();
   Domain* dm = get_dom(dom);
   if (!dm) return fail(H2G_ERR_HANDLE, "unknown domain");
-  const size_t n = 1ull << dm->k;
-  HIPCHK(d->b.ensure(n * 32));
-  HIPCHK(hipMemcpyAsync(d->b.p, a, n * 32, hipMemcpyHostToDevice, d->stream));
-  int rc = h2g_lagrange_to_coeff_dev(dom, d->b.p, nullptr);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(a, d->b.p, n * 32, hipMemcpyDeviceToHost, d->stream));
-  HIPCHK(hipStreamSynchronize(d->stream));
-  return H2G_OK;
+  return host_in_place(1ull << dm->k, a, [&](void* da) { return h2g_lagrange_to_coeff_dev(dom, da, nullptr); });
 }
 
 int h2g_coeff_to_extended(uint64_t dom, const uint64_t* a, uint64_t* out) {
-  Domain* dm;
-  {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    dm = get_dom(dom);
-    if (!dm) return fail(H2G_ERR_HANDLE, "unknown domain");
-  }
-  return host_roundtrip(1ull << dm->k, a, 1ull << dm->ek, out, h2g_coeff_to_extended_dev, dom);
+  NEED_DEV();
+  Domain* dm = get_dom(dom);
+  if (!dm) return fail(H2G_ERR_HANDLE, "unknown domain");
+  return host_roundtrip(1ull << dm->k, a, 1ull << dm->ek, out, false,
+                        [&](void* da, void* dout) { return h2g_coeff_to_extended_dev(dom, da, dout, nullptr); });
 }
 
 int h2g_extended_to_coeff(uint64_t dom, const uint64_t* a, uint64_t* out) {
-  Domain* dm;
-  {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    dm = get_dom(dom);
-    if (!dm) return fail(H2G_ERR_HANDLE, "unknown domain");
-  }
-  return host_roundtrip(1ull << dm->ek, a, (1ull << dm->k) * (dm->j - 1), out, h2g_extended_to_coeff_dev, dom);
+  NEED_DEV();
+  Domain* dm = get_dom(dom);
+  if (!dm) return fail(H2G_ERR_HANDLE, "unknown domain");
+  return host_roundtrip(1ull << dm->ek, a, (1ull << dm->k) * (dm->j - 1), out, false,
+                        [&](void* da, void* dout) { return h2g_extended_to_coeff_dev(dom, da, dout, nullptr); });
 }
 
 int h2g_divide_by_vanishing_poly(uint64_t dom, uint64_t* a) {
   NEED_DEV();
   Domain* dm = get_dom(dom);
   if (!dm) return fail(H2G_ERR_HANDLE, "unknown domain");
-  const size_t n = 1ull << dm->ek;
-  HIPCHK(d->b.ensure(n * 32));
-  HIPCHK(hipMemcpyAsync(d->b.p, a, n * 32, hipMemcpyHostToDevice, d->stream));
-  int rc = h2g_divide_by_vanishing_poly_dev(dom, d->b.p, nullptr);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(a, d->b.p, n * 32, hipMemcpyDeviceToHost, d->stream));
-  HIPCHK(hipStreamSynchronize(d->stream));
-  return H2G_OK;
+  return host_in_place(1ull << dm->ek, a, [&](void* da) { return h2g_divide_by_vanishing_poly_dev(dom, da, nullptr); });
 }
 
 // ---------------------------------------------------------------- poly ops
@@ -870,16 +806,11 @@ int h2g_fr_op_dev(int op, const void* a, const void* b, const uint64_t c[4], voi
 
 int h2g_fr_op(int op, const uint64_t* a, const uint64_t* b, const uint64_t c[4], uint64_t* out, size_t n) {
   NEED_DEV();
-  HIPCHK(d->a.ensure(n * 32 + 32));
-  HIPCHK(d->b.ensure(n * 32 + 32));
-  HIPCHK(d->c.ensure(n * 32 + 32));
-  HIPCHK(hipMemcpyAsync(d->a.p, a, n * 32, hipMemcpyHostToDevice, d->stream));
-  if (b) HIPCHK(hipMemcpyAsync(d->b.p, b, n * 32, hipMemcpyHostToDevice, d->stream));
-  int rc = h2g_fr_op_dev(op, d->a.p, b ? d->b.p : nullptr, c, d->c.p, n, nullptr);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(out, d->c.p, n * 32, hipMemcpyDeviceToHost, d->stream));
-  HIPCHK(hipStreamSynchronize(d->stream));
-  return H2G_OK;
+  HIPCHK(d->a.ensure(n * 32 + 32));  // the second operand; the round trip takes the first
+  if (b) HIPCHK(hipMemcpyAsync(d->a.p, b, n * 32, hipMemcpyHostToDevice, d->stream));
+  return host_roundtrip(n, a, n, out, false, [&](void* da, void* dout) {
+    return h2g_fr_op_dev(op, da, b ? d->a.p : nullptr, c, dout, n, nullptr);
+  });
 }
 
 int h2g_fr_batch_invert_dev(void* a, size_t n, void* stream) {
@@ -891,14 +822,7 @@ int h2g_fr_batch_invert_dev(void* a, size_t n, void* stream) {
 }
 
 int h2g_fr_batch_invert(uint64_t* a, size_t n) {
-  NEED_DEV();
-  HIPCHK(d->a.ensure(n * 32 + 32));
-  HIPCHK(hipMemcpyAsync(d->a.p, a, n * 32, hipMemcpyHostToDevice, d->stream));
-  int rc = h2g_fr_batch_invert_dev(d->a.p, n, nullptr);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(a, d->a.p, n * 32, hipMemcpyDeviceToHost, d->stream));
-  HIPCHK(hipStreamSynchronize(d->stream));
-  return H2G_OK;
+  return host_in_place(n, a, [&](void* da) { return h2g_fr_batch_invert_dev(da, n, nullptr); });
 }
 
 int h2g_fr_prefix_product_dev(const void* a, void* out, size_t n, void* stream) {
@@ -911,15 +835,8 @@ int h2g_fr_prefix_product_dev(const void* a, void* out, size_t n, void* stream) 
 }
 
 int h2g_fr_prefix_product(const uint64_t* a, uint64_t* out, size_t n) {
-  NEED_DEV();
-  HIPCHK(d->a.ensure(n * 32 + 32));
-  HIPCHK(d->c.ensure(n * 32 + 32));
-  HIPCHK(hipMemcpyAsync(d->a.p, a, n * 32, hipMemcpyHostToDevice, d->stream));
-  int rc = h2g_fr_prefix_product_dev(d->a.p, d->c.p, n, nullptr);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(out, d->c.p, n * 32, hipMemcpyDeviceToHost, d->stream));
-  HIPCHK(hipStreamSynchronize(d->stream));
-  return H2G_OK;
+  return host_roundtrip(n, a, n, out, false,
+                        [&](void* da, void* dout) { return h2g_fr_prefix_product_dev(da, dout, n, nullptr); });
 }
 
 // exclusive prefix sum of u32 counts (the lookup argument's compactions and radix sort)

@@ -47,20 +47,20 @@ void add_query(std::vector<Query>& l, const Query& q) {
   if (std::find(l.begin(), l.end(), q) == l.end()) l.push_back(q);
 }
 
-void collect(const CircuitView& v, int i, CsHost& pk) {  // keygen.rs:217-249, lhs before rhs
+void collect(const CircuitView& v, int i, CsHost& cs) {  // keygen.rs:217-249, lhs before rhs
   const int32_t* nd = v.node(i);
   switch (nd[0]) {
     case OP_CONST:
     case OP_CHALLENGE: return;
     case OP_QUERY: {
       const Query q{nd[1], nd[2], nd[3]};
-      add_query(nd[1] == COL_ADVICE ? pk.adv_q : (nd[1] == COL_FIXED ? pk.fix_q : pk.ins_q), q);
+      add_query(nd[1] == COL_ADVICE ? cs.adv_q : (nd[1] == COL_FIXED ? cs.fix_q : cs.ins_q), q);
       return;
     }
-    case OP_NEG: collect(v, nd[1], pk); return;
+    case OP_NEG: collect(v, nd[1], cs); return;
     default:
-      collect(v, nd[1], pk);
-      collect(v, nd[2], pk);
+      collect(v, nd[1], cs);
+      collect(v, nd[2], cs);
       return;
   }
 }
@@ -244,29 +244,29 @@ int circuit_ws_add(ProvingKey& pk) {
     }
     return hipSuccess;
   };
-  HIPCHK(vec_alloc(w->adv, pk.A, n));
-  HIPCHK(vec_alloc(w->adv_poly, pk.A, n));
-  HIPCHK(vec_alloc(w->adv_coset, pk.A, ext));
-  HIPCHK(vec_alloc(w->inst_val, pk.I, n));
-  HIPCHK(vec_alloc(w->inst_poly, pk.I, n));
-  HIPCHK(vec_alloc(w->inst_coset, pk.I, ext));
-  HIPCHK(vec_alloc(w->z, pk.nsets, n));
-  HIPCHK(vec_alloc(w->z_lag, pk.nsets, n));
-  HIPCHK(vec_alloc(w->z_coset, pk.nsets, ext));
-  HIPCHK(vec_alloc(w->lk_a, pk.NL, n));
-  HIPCHK(vec_alloc(w->lk_s, pk.NL, n));
-  HIPCHK(vec_alloc(w->lk_ap, pk.NL, n));
-  HIPCHK(vec_alloc(w->lk_sp, pk.NL, n));
-  HIPCHK(vec_alloc(w->lk_ap_poly, pk.NL, n));
-  HIPCHK(vec_alloc(w->lk_sp_poly, pk.NL, n));
-  HIPCHK(vec_alloc(w->lk_z, pk.NL, n));
-  HIPCHK(vec_alloc(w->lk_z_poly, pk.NL, n));
-  HIPCHK(vec_alloc(w->lk_zc, pk.NL, ext));
-  HIPCHK(vec_alloc(w->lk_apc, pk.NL, ext));
-  HIPCHK(vec_alloc(w->lk_spc, pk.NL, ext));
-  HIPCHK(vec_alloc(w->sh_z, pk.NS, n));
-  HIPCHK(vec_alloc(w->sh_z_poly, pk.NS, n));
-  HIPCHK(vec_alloc(w->sh_zc, pk.NS, ext));
+  HIPCHK(vec_alloc(w->adv, pk.cs.A, n));
+  HIPCHK(vec_alloc(w->adv_poly, pk.cs.A, n));
+  HIPCHK(vec_alloc(w->adv_coset, pk.cs.A, ext));
+  HIPCHK(vec_alloc(w->inst_val, pk.cs.I, n));
+  HIPCHK(vec_alloc(w->inst_poly, pk.cs.I, n));
+  HIPCHK(vec_alloc(w->inst_coset, pk.cs.I, ext));
+  HIPCHK(vec_alloc(w->z, pk.cs.nsets, n));
+  HIPCHK(vec_alloc(w->z_lag, pk.cs.nsets, n));
+  HIPCHK(vec_alloc(w->z_coset, pk.cs.nsets, ext));
+  HIPCHK(vec_alloc(w->lk_a, pk.cs.NL, n));
+  HIPCHK(vec_alloc(w->lk_s, pk.cs.NL, n));
+  HIPCHK(vec_alloc(w->lk_ap, pk.cs.NL, n));
+  HIPCHK(vec_alloc(w->lk_sp, pk.cs.NL, n));
+  HIPCHK(vec_alloc(w->lk_ap_poly, pk.cs.NL, n));
+  HIPCHK(vec_alloc(w->lk_sp_poly, pk.cs.NL, n));
+  HIPCHK(vec_alloc(w->lk_z, pk.cs.NL, n));
+  HIPCHK(vec_alloc(w->lk_z_poly, pk.cs.NL, n));
+  HIPCHK(vec_alloc(w->lk_zc, pk.cs.NL, ext));
+  HIPCHK(vec_alloc(w->lk_apc, pk.cs.NL, ext));
+  HIPCHK(vec_alloc(w->lk_spc, pk.cs.NL, ext));
+  HIPCHK(vec_alloc(w->sh_z, pk.cs.NS, n));
+  HIPCHK(vec_alloc(w->sh_z_poly, pk.cs.NS, n));
+  HIPCHK(vec_alloc(w->sh_zc, pk.cs.NS, ext));
   // pointer tables: the load table's columns for this circuit (fixed columns are shared)
   auto col = [&](const Query& q, bool coset) -> const Fr* {
     if (q.type == COL_ADVICE) return coset ? w->adv_coset[q.index] : w->adv[q.index];
@@ -278,13 +278,13 @@ int circuit_ws_add(ProvingKey& pk) {
     lc[i] = col(pk.loads[i], true);
     ll[i] = col(pk.loads[i], false);
   }
-  std::vector<EvalLookup> el(pk.NL + 1);
-  std::vector<EvalShuffle> es(pk.NS + 1);
-  for (int l = 0; l < pk.NL; l++) el[l] = EvalLookup{pk.seg_lk_in[l], pk.seg_lk_tab[l], w->lk_zc[l], w->lk_apc[l], w->lk_spc[l]};
-  for (int l = 0; l < pk.NS; l++) es[l] = EvalShuffle{pk.seg_sh_in[l], pk.seg_sh_sh[l], w->sh_zc[l]};
-  std::vector<const Fr*> zt(pk.nsets + 1), pv(pk.P + 1);
-  for (int s = 0; s < pk.nsets; s++) zt[s] = w->z_coset[s];
-  for (int i = 0; i < pk.P; i++) pv[i] = col(Query{pk.perm_cols[i].first, pk.perm_cols[i].second, 0}, true);
+  std::vector<EvalLookup> el(pk.cs.NL + 1);
+  std::vector<EvalShuffle> es(pk.cs.NS + 1);
+  for (int l = 0; l < pk.cs.NL; l++) el[l] = EvalLookup{pk.seg_lk_in[l], pk.seg_lk_tab[l], w->lk_zc[l], w->lk_apc[l], w->lk_spc[l]};
+  for (int l = 0; l < pk.cs.NS; l++) es[l] = EvalShuffle{pk.seg_sh_in[l], pk.seg_sh_sh[l], w->sh_zc[l]};
+  std::vector<const Fr*> zt(pk.cs.nsets + 1), pv(pk.cs.P + 1);
+  for (int s = 0; s < pk.cs.nsets; s++) zt[s] = w->z_coset[s];
+  for (int i = 0; i < pk.cs.P; i++) pv[i] = col(Query{pk.cs.perm_cols[i].first, pk.cs.perm_cols[i].second, 0}, true);
   PALLOC(w->pool, w->d_load_col, lc.size());
   PALLOC(w->pool, w->d_load_col_lag, ll.size());
   PALLOC(w->pool, w->d_lookups, el.size());
@@ -325,8 +325,8 @@ int build_pow_table(Pool& pool, const Fr& w, int L, PowTable* t, hipStream_t st)
 
 // the constraint system's shape and a host copy of its expressions
 int cs_host_build(const h2g_circuit* c, CsHost* out) {
-  CsHost& pk = *out;
-  pk = CsHost{};
+  CsHost& cs = *out;
+  cs = CsHost{};
   std::string why;
   if (c->num_gates && (!c->gate_roots || !c->nodes)) return fail(H2G_ERR_ARG, "keygen: null gates");
   if (!check_nodes(c, &why)) return fail(H2G_ERR_ARG, "keygen: bad expression graph: " + why);
@@ -334,44 +334,44 @@ int cs_host_build(const h2g_circuit* c, CsHost* out) {
   if (c->k > FR_S) return fail(H2G_ERR_ARG, "keygen: k too large");
   const CircuitView cv{c};
   const size_t n = (size_t)1 << c->k;
-  pk.k = c->k;
-  pk.A = (int)c->num_advice;
-  pk.F = (int)c->num_fixed;
-  pk.I = (int)c->num_instance;
-  pk.P = (int)c->num_perm_columns;
-  pk.transcript_repr = fr_from_limbs(c->transcript_repr);
-  pk.adv_phase.assign(pk.A, 0);
+  cs.k = c->k;
+  cs.A = (int)c->num_advice;
+  cs.F = (int)c->num_fixed;
+  cs.I = (int)c->num_instance;
+  cs.P = (int)c->num_perm_columns;
+  cs.transcript_repr = fr_from_limbs(c->transcript_repr);
+  cs.adv_phase.assign(cs.A, 0);
   if (c->advice_phase)
-    for (int i = 0; i < pk.A; i++) pk.adv_phase[i] = c->advice_phase[i];
-  pk.ch_phase.assign(c->num_challenges, 0);
+    for (int i = 0; i < cs.A; i++) cs.adv_phase[i] = c->advice_phase[i];
+  cs.ch_phase.assign(c->num_challenges, 0);
   if (c->num_challenges && !c->challenge_phase) return fail(H2G_ERR_ARG, "keygen: null challenge_phase");
-  for (uint32_t i = 0; i < c->num_challenges; i++) pk.ch_phase[i] = c->challenge_phase[i];
-  pk.max_phase = 0;
-  for (int i = 0; i < pk.A; i++) pk.max_phase = std::max(pk.max_phase, (int)pk.adv_phase[i]);
-  for (uint8_t ph : pk.ch_phase)
-    if ((int)ph > pk.max_phase) return fail(H2G_ERR_ARG, "keygen: challenge phase after the last advice phase");
-  if (pk.P && !c->perm_columns) return fail(H2G_ERR_ARG, "keygen: null permutation columns");
-  for (int i = 0; i < pk.P; i++) {
+  for (uint32_t i = 0; i < c->num_challenges; i++) cs.ch_phase[i] = c->challenge_phase[i];
+  cs.max_phase = 0;
+  for (int i = 0; i < cs.A; i++) cs.max_phase = std::max(cs.max_phase, (int)cs.adv_phase[i]);
+  for (uint8_t ph : cs.ch_phase)
+    if ((int)ph > cs.max_phase) return fail(H2G_ERR_ARG, "keygen: challenge phase after the last advice phase");
+  if (cs.P && !c->perm_columns) return fail(H2G_ERR_ARG, "keygen: null permutation columns");
+  for (int i = 0; i < cs.P; i++) {
     const int t = c->perm_columns[2 * i], ix = c->perm_columns[2 * i + 1];
-    const int lim = t == COL_ADVICE ? pk.A : t == COL_FIXED ? pk.F : t == COL_INSTANCE ? pk.I : 0;
+    const int lim = t == COL_ADVICE ? cs.A : t == COL_FIXED ? cs.F : t == COL_INSTANCE ? cs.I : 0;
     if (ix < 0 || ix >= lim) return fail(H2G_ERR_ARG, "keygen: permutation column out of range");
-    pk.perm_cols.emplace_back(t, ix);
+    cs.perm_cols.emplace_back(t, ix);
   }
   // degree, queries, blinding factors (circuit.rs:143-170,292-320; keygen.rs:191-260)
   std::vector<int> memo(c->num_nodes, -1);
   const std::vector<ArgRoots> lks = arg_roots(c->num_lookups, c->lookup_sizes, c->lookup_roots);
   const std::vector<ArgRoots> shs = arg_roots(c->num_shuffles, c->shuffle_sizes, c->shuffle_roots);
-  pk.NL = (int)lks.size();
-  pk.NS = (int)shs.size();
-  pk.degree = 3;
-  for (uint32_t g = 0; g < c->num_gates; g++) pk.degree = std::max(pk.degree, node_degree(cv, c->gate_roots[g], memo));
+  cs.NL = (int)lks.size();
+  cs.NS = (int)shs.size();
+  cs.degree = 3;
+  for (uint32_t g = 0; g < c->num_gates; g++) cs.degree = std::max(cs.degree, node_degree(cv, c->gate_roots[g], memo));
   for (const auto& a : lks) {  // lookup_argument_required_degree (circuit.rs:327-373)
     int di = 1, dt = 1;
     for (int i = 0; i < a.m; i++) {
       di = std::max(di, node_degree(cv, a.in[i], memo));
       dt = std::max(dt, node_degree(cv, a.other[i], memo));
     }
-    pk.degree = std::max(pk.degree, std::max(4, 2 + di + dt));
+    cs.degree = std::max(cs.degree, std::max(4, 2 + di + dt));
   }
   for (const auto& a : shs) {  // shuffle_argument_required_degree (circuit.rs:375-389)
     int di = 1, ds = 1;
@@ -379,44 +379,44 @@ int cs_host_build(const h2g_circuit* c, CsHost* out) {
       di = std::max(di, node_degree(cv, a.in[i], memo));
       ds = std::max(ds, node_degree(cv, a.other[i], memo));
     }
-    pk.degree = std::max(pk.degree, 2 + std::max(di, ds));
+    cs.degree = std::max(cs.degree, 2 + std::max(di, ds));
   }
   // queries: gates, lookups (inputs then tables), shuffles, permutation (keygen.rs:320-345)
-  for (uint32_t g = 0; g < c->num_gates; g++) collect(cv, c->gate_roots[g], pk);
+  for (uint32_t g = 0; g < c->num_gates; g++) collect(cv, c->gate_roots[g], cs);
   for (const auto& a : lks) {
-    for (int i = 0; i < a.m; i++) collect(cv, a.in[i], pk);
-    for (int i = 0; i < a.m; i++) collect(cv, a.other[i], pk);
+    for (int i = 0; i < a.m; i++) collect(cv, a.in[i], cs);
+    for (int i = 0; i < a.m; i++) collect(cv, a.other[i], cs);
   }
   for (const auto& a : shs) {
-    for (int i = 0; i < a.m; i++) collect(cv, a.in[i], pk);
-    for (int i = 0; i < a.m; i++) collect(cv, a.other[i], pk);
+    for (int i = 0; i < a.m; i++) collect(cv, a.in[i], cs);
+    for (int i = 0; i < a.m; i++) collect(cv, a.other[i], cs);
   }
-  for (auto& pc : pk.perm_cols)
-    add_query(pc.first == COL_ADVICE ? pk.adv_q : (pc.first == COL_FIXED ? pk.fix_q : pk.ins_q),
+  for (auto& pc : cs.perm_cols)
+    add_query(pc.first == COL_ADVICE ? cs.adv_q : (pc.first == COL_FIXED ? cs.fix_q : cs.ins_q),
               Query{pc.first, pc.second, 0});
   int maxq = 1;
-  if (pk.A) {
-    std::vector<int> cnt(pk.A, 0);
-    for (auto& q : pk.adv_q) cnt[q.index]++;
+  if (cs.A) {
+    std::vector<int> cnt(cs.A, 0);
+    for (auto& q : cs.adv_q) cnt[q.index]++;
     maxq = *std::max_element(cnt.begin(), cnt.end());
   }
-  pk.bf = std::max(3, maxq) + 2;
-  if ((int64_t)n < pk.bf + 3) return fail(H2G_ERR_ARG, "keygen: not enough rows available");
-  pk.chunk_len = pk.degree - 2;
-  pk.nsets = (pk.P + pk.chunk_len - 1) / pk.chunk_len;
+  cs.bf = std::max(3, maxq) + 2;
+  if ((int64_t)n < cs.bf + 3) return fail(H2G_ERR_ARG, "keygen: not enough rows available");
+  cs.chunk_len = cs.degree - 2;
+  cs.nsets = (cs.P + cs.chunk_len - 1) / cs.chunk_len;
   // the host copy of the expression graph
-  if (c->num_nodes) pk.nodes.assign(c->nodes, c->nodes + 4 * (size_t)c->num_nodes);
+  if (c->num_nodes) cs.nodes.assign(c->nodes, c->nodes + 4 * (size_t)c->num_nodes);
   if (c->num_constants && !c->constants) return fail(H2G_ERR_ARG, "keygen: null constants");
-  pk.constants.resize(c->num_constants);
-  for (uint32_t i = 0; i < c->num_constants; i++) pk.constants[i] = fr_from_limbs(c->constants + 4 * i);
-  if (c->num_gates) pk.gate_roots.assign(c->gate_roots, c->gate_roots + c->num_gates);
+  cs.constants.resize(c->num_constants);
+  for (uint32_t i = 0; i < c->num_constants; i++) cs.constants[i] = fr_from_limbs(c->constants + 4 * i);
+  if (c->num_gates) cs.gate_roots.assign(c->gate_roots, c->gate_roots + c->num_gates);
   for (const auto& a : lks) {
-    pk.lk_in.emplace_back(a.in, a.in + a.m);
-    pk.lk_tab.emplace_back(a.other, a.other + a.m);
+    cs.lk_in.emplace_back(a.in, a.in + a.m);
+    cs.lk_tab.emplace_back(a.other, a.other + a.m);
   }
   for (const auto& a : shs) {
-    pk.sh_in.emplace_back(a.in, a.in + a.m);
-    pk.sh_sh.emplace_back(a.other, a.other + a.m);
+    cs.sh_in.emplace_back(a.in, a.in + a.m);
+    cs.sh_sh.emplace_back(a.other, a.other + a.m);
   }
   return H2G_OK;
 }
@@ -429,40 +429,18 @@ int keygen_impl(Device* d, Params& prm, const h2g_circuit* c, ProvingKey& pk, co
   const CircuitView cv{c};
   const std::vector<ArgRoots> lks = arg_roots(c->num_lookups, c->lookup_sizes, c->lookup_roots);
   const std::vector<ArgRoots> shs = arg_roots(c->num_shuffles, c->shuffle_sizes, c->shuffle_roots);
-  {
-    const CsHost& cs = pk.cs;
-    pk.device = d->id;
-    pk.k = cs.k;
-    pk.n = (size_t)1 << cs.k;
-    pk.A = cs.A;
-    pk.F = cs.F;
-    pk.I = cs.I;
-    pk.P = cs.P;
-    pk.NL = cs.NL;
-    pk.NS = cs.NS;
-    pk.transcript_repr = cs.transcript_repr;
-    pk.unblinded.assign(pk.A, 0);
-    if (c->unblinded)
-      for (int i = 0; i < pk.A; i++) pk.unblinded[i] = c->unblinded[i];
-    pk.adv_phase = cs.adv_phase;
-    pk.ch_phase = cs.ch_phase;
-    pk.max_phase = cs.max_phase;
-    pk.num_consts = (int)c->num_constants;
-    pk.perm_cols = cs.perm_cols;
-    pk.degree = cs.degree;
-    pk.adv_q = cs.adv_q;
-    pk.fix_q = cs.fix_q;
-    pk.ins_q = cs.ins_q;
-    pk.bf = cs.bf;
-    pk.chunk_len = cs.chunk_len;
-    pk.nsets = cs.nsets;
-  }
-  RCCHK(domain_init(&pk.dom, (uint32_t)pk.degree, pk.k));
+  pk.device = d->id;
+  pk.n = (size_t)1 << pk.cs.k;
+  pk.unblinded.assign(pk.cs.A, 0);
+  if (c->unblinded)
+    for (int i = 0; i < pk.cs.A; i++) pk.unblinded[i] = c->unblinded[i];
+  pk.num_consts = (int)c->num_constants;
+  RCCHK(domain_init(&pk.dom, (uint32_t)pk.cs.degree, pk.cs.k));
   pk.ext = (size_t)1 << pk.dom.ek;
-  pk.rot_scale = 1ull << (pk.dom.ek - pk.k);
+  pk.rot_scale = 1ull << (pk.dom.ek - pk.cs.k);
   const size_t n = pk.n, ext = pk.ext;
   Pool& pool = pk.pool;
-  RCCHK(build_pow_table(pool, pk.dom.omega, (int)pk.k, &pk.om, st));
+  RCCHK(build_pow_table(pool, pk.dom.omega, (int)pk.cs.k, &pk.om, st));
   RCCHK(build_pow_table(pool, pk.dom.ext_omega, (int)pk.dom.ek, &pk.eo, st));
 
   // workspace first (keygen uses some of it as scratch)
@@ -494,11 +472,11 @@ int keygen_impl(Device* d, Params& prm, const h2g_circuit* c, ProvingKey& pk, co
     const Fr one = Fr::one();
     HIPCHK(hipMemcpy(pk.one, &one, sizeof(Fr), hipMemcpyHostToDevice));
   }
-  if (pk.NL + pk.NS) {
+  if (pk.cs.NL + pk.cs.NS) {
     HIPCHK(falloc(&pk.tmp_a, n));
     HIPCHK(falloc(&pk.tmp_b, n));
   }
-  if (pk.NL) {  // permute_expression_pair scratch (the batched sort's buffers grow per proof)
+  if (pk.cs.NL) {  // permute_expression_pair scratch (the batched sort's buffers grow per proof)
     PALLOC(pool, pk.ck_a2, n);
     PALLOC(pool, pk.ck_t2, n);
     PALLOC(pool, pk.ck_left, n);
@@ -506,14 +484,14 @@ int keygen_impl(Device* d, Params& prm, const h2g_circuit* c, ProvingKey& pk, co
     PALLOC(pool, pk.left_flag, n);
     PALLOC(pool, pk.rep_rows, n);
     PALLOC(pool, pk.counters, 8);
-    pk.lk_hb.assign(pk.NL, 64);
+    pk.lk_hb.assign(pk.cs.NL, 64);
   }
 
   // fixed columns
-  HIPCHK(vec_alloc(pk.fixed_lag, pk.F, n));
-  HIPCHK(vec_alloc(pk.fixed_poly, pk.F, n));
-  HIPCHK(vec_alloc(pk.fixed_coset, pk.F, ext));
-  for (int i = 0; i < pk.F; i++) {
+  HIPCHK(vec_alloc(pk.fixed_lag, pk.cs.F, n));
+  HIPCHK(vec_alloc(pk.fixed_poly, pk.cs.F, n));
+  HIPCHK(vec_alloc(pk.fixed_coset, pk.cs.F, ext));
+  for (int i = 0; i < pk.cs.F; i++) {
     if (img) {
       HIPCHK(img->upload(pk.fixed_lag[i], img->fixed_lag[i], n, st));
       HIPCHK(img->upload(pk.fixed_poly[i], img->fixed_poly[i], n, st));
@@ -534,7 +512,7 @@ int keygen_impl(Device* d, Params& prm, const h2g_circuit* c, ProvingKey& pk, co
     HIPCHK(img->upload(pk.l_active, img->l_active, ext, st));
   } else {
     const Fr one = Fr::one();
-    std::vector<Fr> ones(pk.bf, one);
+    std::vector<Fr> ones(pk.cs.bf, one);
     auto lagrange_unit = [&](size_t row0, int count, Fr* out) -> int {
       HIPCHK(hipMemsetAsync(pk.pre, 0, n * sizeof(Fr), st));
       HIPCHK(hipMemcpyAsync(pk.pre + row0, ones.data(), count * sizeof(Fr), hipMemcpyHostToDevice, st));
@@ -544,35 +522,35 @@ int keygen_impl(Device* d, Params& prm, const h2g_circuit* c, ProvingKey& pk, co
       return H2G_OK;
     };
     RCCHK(lagrange_unit(0, 1, pk.l0));
-    RCCHK(lagrange_unit(n - pk.bf, pk.bf, pk.h_ext));  // l_blind
-    RCCHK(lagrange_unit(n - pk.bf - 1, 1, pk.l_last));
+    RCCHK(lagrange_unit(n - pk.cs.bf, pk.cs.bf, pk.h_ext));  // l_blind
+    RCCHK(lagrange_unit(n - pk.cs.bf - 1, 1, pk.l_last));
     HIPCHK(poly_binop(POLY_ADD, pk.l_last, pk.h_ext, one, pk.l_active, ext, st));
     HIPCHK(poly_binop(POLY_SUB_CONST, pk.l_active, nullptr, one, pk.l_active, ext, st));
     HIPCHK(poly_binop(POLY_SCALE, pk.l_active, nullptr, fr_neg_one(), pk.l_active, ext, st));
   }
   // permutation: Assembly on the host, sigma polynomials on the device
-  HIPCHK(vec_alloc(pk.sigma_lag, pk.P, n));
-  HIPCHK(vec_alloc(pk.sigma_poly, pk.P, n));
-  HIPCHK(vec_alloc(pk.sigma_coset, pk.P, ext));
-  if (pk.P && img) {
-    for (int i = 0; i < pk.P; i++) {
+  HIPCHK(vec_alloc(pk.sigma_lag, pk.cs.P, n));
+  HIPCHK(vec_alloc(pk.sigma_poly, pk.cs.P, n));
+  HIPCHK(vec_alloc(pk.sigma_coset, pk.cs.P, ext));
+  if (pk.cs.P && img) {
+    for (int i = 0; i < pk.cs.P; i++) {
       HIPCHK(img->upload(pk.sigma_lag[i], img->sigma_lag[i], n, st));
       HIPCHK(img->upload(pk.sigma_poly[i], img->sigma_poly[i], n, st));
       HIPCHK(img->upload(pk.sigma_coset[i], img->sigma_coset[i], ext, st));
     }
     HIPCHK(hipStreamSynchronize(st));
-  } else if (pk.P) {
-    const size_t cells = (size_t)pk.P * n;
+  } else if (pk.cs.P) {
+    const size_t cells = (size_t)pk.cs.P * n;
     std::vector<uint32_t> mcol(cells), mrow(cells), acol(cells), arow(cells);
     std::vector<uint64_t> sizes(cells, 1);
-    for (int cI = 0; cI < pk.P; cI++)
+    for (int cI = 0; cI < pk.cs.P; cI++)
       for (size_t r = 0; r < n; r++) {
         mcol[cI * n + r] = acol[cI * n + r] = (uint32_t)cI;
         mrow[cI * n + r] = arow[cI * n + r] = (uint32_t)r;
       }
     auto pos = [&](int t, int ix) -> int {
-      for (int i = 0; i < pk.P; i++)
-        if (pk.perm_cols[i].first == t && pk.perm_cols[i].second == ix) return i;
+      for (int i = 0; i < pk.cs.P; i++)
+        if (pk.cs.perm_cols[i].first == t && pk.cs.perm_cols[i].second == ix) return i;
       return -1;
     };
     for (uint32_t ci = 0; ci < c->num_copies; ci++) {  // Assembly::copy (permutation/keygen.rs:59-97)
@@ -596,9 +574,9 @@ int keygen_impl(Device* d, Params& prm, const h2g_circuit* c, ProvingKey& pk, co
       std::swap(mcol[li], mcol[ri]);
       std::swap(mrow[li], mrow[ri]);
     }
-    std::vector<Fr> dpow(pk.P + 1);
+    std::vector<Fr> dpow(pk.cs.P + 1);
     dpow[0] = Fr::one();
-    for (int i = 1; i <= pk.P; i++) dpow[i] = dpow[i - 1] * fr_delta();
+    for (int i = 1; i <= pk.cs.P; i++) dpow[i] = dpow[i - 1] * fr_delta();
     uint32_t *dmc, *dmr;
     Fr* ddp;
     HIPCHK(hipMalloc(&dmc, cells * 4));
@@ -607,7 +585,7 @@ int keygen_impl(Device* d, Params& prm, const h2g_circuit* c, ProvingKey& pk, co
     HIPCHK(hipMemcpyAsync(dmc, mcol.data(), cells * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(dmr, mrow.data(), cells * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(ddp, dpow.data(), dpow.size() * sizeof(Fr), hipMemcpyHostToDevice, st));
-    for (int i = 0; i < pk.P; i++) {
+    for (int i = 0; i < pk.cs.P; i++) {
       HIPCHK(sigma_from_mapping(pk.sigma_lag[i], dmc + i * n, dmr + i * n, n, ddp, pk.om, st));
       RCCHK(lagrange_to_coeff(d, pk.dom, pk.sigma_lag[i], pk.sigma_poly[i], st));
       RCCHK(coeff_to_extended(d, pk.dom, pk.sigma_poly[i], pk.sigma_coset[i], st));
@@ -664,8 +642,8 @@ int keygen_impl(Device* d, Params& prm, const h2g_circuit* c, ProvingKey& pk, co
     for (int i = 0; i < pk.n_loads; i++) lr[i] = gc.loads[i].rot;
     PALLOC(pool, pk.d_load_rot, lr.size());
     HIPCHK(hipMemcpy(pk.d_load_rot, lr.data(), lr.size() * sizeof(int), hipMemcpyHostToDevice));
-    std::vector<const Fr*> sg(pk.P + 1);
-    for (int i = 0; i < pk.P; i++) sg[i] = pk.sigma_coset[i];
+    std::vector<const Fr*> sg(pk.cs.P + 1);
+    for (int i = 0; i < pk.cs.P; i++) sg[i] = pk.sigma_coset[i];
     PALLOC(pool, pk.d_sigma, sg.size());
     HIPCHK(hipMemcpy(pk.d_sigma, sg.data(), sg.size() * sizeof(Fr*), hipMemcpyHostToDevice));
   }
@@ -680,18 +658,15 @@ extern "C" {
 
 int h2g_keygen(uint64_t params, const h2g_circuit* circuit, uint64_t* pk_out) {
   NEED_DEV_P();
-  auto it = g_params.find(params);
-  if (it == g_params.end()) return fail(H2G_ERR_HANDLE, "unknown params");
+  Params* it = find_params(params);
+  if (!it) return fail(H2G_ERR_HANDLE, "unknown params");
   if (!circuit || !pk_out) return fail(H2G_ERR_ARG, "keygen: null argument");
   auto pk = std::make_unique<ProvingKey>();
   pk->params = params;
-  int rc = keygen_impl(d, *it->second, circuit, *pk);
+  int rc = keygen_impl(d, *it, circuit, *pk);
   // the lookup commitments' basis (params_prefix) now, not inside the first proof
-  if (!rc && circuit->num_lookups > 0) rc = params_prefix(*it->second, d->stream);
-  if (rc) {
-    domain_release(&pk->dom);
-    return rc;
-  }
+  if (!rc && circuit->num_lookups > 0) rc = params_prefix(*it, d->stream);
+  if (rc) return rc;
   *pk_out = g_next_handle++;
   g_pks[*pk_out] = std::move(pk);
   return H2G_OK;
@@ -699,25 +674,11 @@ int h2g_keygen(uint64_t params, const h2g_circuit* circuit, uint64_t* pk_out) {
 
 int h2g_pk_free(uint64_t pk) {
   NEED_DEV_P();
-  auto it = g_pks.find(pk);
-  if (it == g_pks.end()) return fail(H2G_ERR_HANDLE, "unknown proving key");
+  ProvingKey* it = find_pk(pk);
+  if (!it) return fail(H2G_ERR_HANDLE, "unknown proving key");
   (void)hipStreamSynchronize(d->stream);
-  xp_drain(*it->second);
-  for (auto& x : it->second->xp)
-    if (x.done) (void)hipEventDestroy(x.done);
-  domain_release(&it->second->dom);
-  if (it->second->lk_cnt) (void)hipHostFree(it->second->lk_cnt);
-  if (it->second->lk_or_h) (void)hipHostFree(it->second->lk_or_h);
-  if (it->second->lk_or_d) (void)hipFree(it->second->lk_or_d);
-  if (it->second->wsum_h) (void)hipHostFree(it->second->wsum_h);
-  if (it->second->wsum_d) (void)hipFree(it->second->wsum_d);
-  if (it->second->wsum_ev) (void)hipEventDestroy(it->second->wsum_ev);
-  for (hipStream_t q : it->second->lk_st)
-    if (q) (void)hipStreamDestroy(q);
-  for (hipEvent_t e : it->second->lk_ev)
-    if (e) (void)hipEventDestroy(e);
-  if (it->second->up_h) (void)hipHostFree(it->second->up_h);
-  g_pks.erase(it);
+  xp_drain(*it);
+  g_pks.erase(pk);
   return H2G_OK;
 }
 
@@ -726,59 +687,59 @@ int h2g_pk_free(uint64_t pk) {
  * (keygen.rs, permutation/keygen.rs:269), computed once */
 int h2g_pk_vk_commitments(uint64_t pk_h, uint64_t* fixed, uint64_t* perm) {
   NEED_DEV_P();
-  auto it = g_pks.find(pk_h);
-  if (it == g_pks.end()) return fail(H2G_ERR_HANDLE, "unknown proving key");
-  ProvingKey& pk = *it->second;
-  auto pit = g_params.find(pk.params);
-  if (pit == g_params.end()) return fail(H2G_ERR_HANDLE, "pk_vk_commitments: the key's params were freed");
-  if (pk.vk_fixed.size() != (size_t)pk.F || pk.vk_perm.size() != (size_t)pk.P) {
-    std::vector<G1Affine> f(pk.F), q(pk.P);
-    for (int i = 0; i < pk.F; i++) RCCHK(commit(d, *pit->second, pk.fixed_lag[i], pk.n, SRS_LAGRANGE, &f[i], d->stream));
-    for (int i = 0; i < pk.P; i++) RCCHK(commit(d, *pit->second, pk.sigma_lag[i], pk.n, SRS_LAGRANGE, &q[i], d->stream));
+  ProvingKey* it = find_pk(pk_h);
+  if (!it) return fail(H2G_ERR_HANDLE, "unknown proving key");
+  ProvingKey& pk = *it;
+  Params* pit = find_params(pk.params);
+  if (!pit) return fail(H2G_ERR_HANDLE, "pk_vk_commitments: the key's params were freed");
+  if (pk.vk_fixed.size() != (size_t)pk.cs.F || pk.vk_perm.size() != (size_t)pk.cs.P) {
+    std::vector<G1Affine> f(pk.cs.F), q(pk.cs.P);
+    for (int i = 0; i < pk.cs.F; i++) RCCHK(commit(d, *pit, pk.fixed_lag[i], pk.n, SRS_LAGRANGE, &f[i], d->stream));
+    for (int i = 0; i < pk.cs.P; i++) RCCHK(commit(d, *pit, pk.sigma_lag[i], pk.n, SRS_LAGRANGE, &q[i], d->stream));
     pk.vk_fixed = f;
     pk.vk_perm = q;
   }
-  if (fixed && pk.F) std::memcpy(fixed, pk.vk_fixed.data(), pk.vk_fixed.size() * sizeof(G1Affine));
-  if (perm && pk.P) std::memcpy(perm, pk.vk_perm.data(), pk.vk_perm.size() * sizeof(G1Affine));
+  if (fixed && pk.cs.F) std::memcpy(fixed, pk.vk_fixed.data(), pk.vk_fixed.size() * sizeof(G1Affine));
+  if (perm && pk.cs.P) std::memcpy(perm, pk.vk_perm.data(), pk.vk_perm.size() * sizeof(G1Affine));
   return H2G_OK;
 }
 
 int h2g_pk_set_multiopen(uint64_t pk, int scheme) {
   NEED_DEV_P();
-  auto it = g_pks.find(pk);
-  if (it == g_pks.end()) return fail(H2G_ERR_HANDLE, "unknown proving key");
+  ProvingKey* it = find_pk(pk);
+  if (!it) return fail(H2G_ERR_HANDLE, "unknown proving key");
   if (scheme != 0 && scheme != 1) return fail(H2G_ERR_ARG, "pk_set_multiopen: scheme must be 0 (SHPLONK) or 1 (GWC)");
-  it->second->multiopen = scheme;
+  it->multiopen = scheme;
   return H2G_OK;
 }
 
 int h2g_pk_set_transcript(uint64_t pk, int kind) {
   NEED_DEV_P();
-  auto it = g_pks.find(pk);
-  if (it == g_pks.end()) return fail(H2G_ERR_HANDLE, "unknown proving key");
+  ProvingKey* it = find_pk(pk);
+  if (!it) return fail(H2G_ERR_HANDLE, "unknown proving key");
   if (kind != TRANSCRIPT_BLAKE2B && kind != TRANSCRIPT_KECCAK256)
     return fail(H2G_ERR_ARG, "pk_set_transcript: kind must be 0 (Blake2bWrite) or 1 (Keccak256Write)");
-  it->second->transcript = kind;
+  it->transcript = kind;
   return H2G_OK;
 }
 
 int h2g_pk_info(uint64_t pk, int32_t info[8]) {
   std::lock_guard<std::recursive_mutex> lk(g_mu);
-  auto it = g_pks.find(pk);
-  if (it == g_pks.end()) return fail(H2G_ERR_HANDLE, "unknown proving key");
-  const ProvingKey& p = *it->second;
-  const int32_t v[8] = {p.degree, p.bf, (int32_t)p.dom.ek, p.nsets, (int32_t)p.adv_q.size(),
-                        (int32_t)p.fix_q.size(), (int32_t)p.ins_q.size(), p.n_slots};
+  ProvingKey* it = find_pk(pk);
+  if (!it) return fail(H2G_ERR_HANDLE, "unknown proving key");
+  const ProvingKey& p = *it;
+  const int32_t v[8] = {p.cs.degree, p.cs.bf, (int32_t)p.dom.ek, p.cs.nsets, (int32_t)p.cs.adv_q.size(),
+                        (int32_t)p.cs.fix_q.size(), (int32_t)p.cs.ins_q.size(), p.n_slots};
   std::memcpy(info, v, sizeof(v));
   return H2G_OK;
 }
 
 int h2g_pk_lookup_sort_hints(uint64_t pk, int32_t* out, int max, int* count) {
   std::lock_guard<std::recursive_mutex> lk(g_mu);
-  auto it = g_pks.find(pk);
-  if (it == g_pks.end()) return fail(H2G_ERR_HANDLE, "unknown proving key");
+  ProvingKey* it = find_pk(pk);
+  if (!it) return fail(H2G_ERR_HANDLE, "unknown proving key");
   if (!count || max < 0 || (max > 0 && !out)) return fail(H2G_ERR_ARG, "pk_lookup_sort_hints: bad arguments");
-  const std::vector<int>& hb = it->second->lk_hb;
+  const std::vector<int>& hb = it->lk_hb;
   *count = (int)hb.size();
   for (int i = 0; i < max && i < (int)hb.size(); i++) out[i] = (int32_t)hb[i];
   return H2G_OK;

@@ -58,10 +58,6 @@ bool point_arg(const uint64_t p[8], G1Affine* out) {
   if (!fq_reduced(out->x) || !fq_reduced(out->y) || out->is_identity()) return false;
   return sqr(out->y) == sqr(out->x) * out->x + from_u64<FqParams>(3);
 }
-TranscriptObj* find_transcript(uint64_t t) {
-  auto it = g_transcripts.find(t);
-  return it == g_transcripts.end() ? nullptr : it->second.get();
-}
 #define NEED_TRANSCRIPT(t)                                  \
   std::lock_guard<std::recursive_mutex> _lk(g_mu);          \
   TranscriptObj* T = find_transcript(t);                    \
@@ -70,8 +66,8 @@ TranscriptObj* find_transcript(uint64_t t) {
 // h2g_multiopen_prove's device scratch, kept with the params (grow-only; freed with them)
 struct MultiopenWs {
   Pool pool;
-  Fr *nx = nullptr, *hx = nullptr, *lx = nullptr, *q1 = nullptr, *scr = nullptr, *small = nullptr;
-  size_t small_len = 0;
+  Fr *nx = nullptr, *hx = nullptr, *lx = nullptr, *q1 = nullptr, *scr = nullptr;
+  DevArr<Fr> small;
   std::vector<Fr*> gwc_q;
 };
 
@@ -91,9 +87,9 @@ int commit_impl(Device* d, Params& prm, int set, const Fr* d_scalars, size_t len
 int commit_entry(uint64_t params, int set, const void* scalars, bool on_device, size_t len, uint64_t out[8],
                  int* is_identity, void* stream) {
   NEED_DEV_P();
-  auto ip = g_params.find(params);
-  if (ip == g_params.end()) return fail(H2G_ERR_HANDLE, "unknown params");
-  Params& prm = *ip->second;
+  Params* ip = find_params(params);
+  if (!ip) return fail(H2G_ERR_HANDLE, "unknown params");
+  Params& prm = *ip;
   if (prm.device != d->id) return fail(H2G_ERR_ARG, "commit: params live on another device");
   if (!out || (len && !scalars)) return fail(H2G_ERR_ARG, "commit: null argument");
   if (len > prm.n) return fail(H2G_ERR_ARG, "commit: more coefficients than the params have points");
@@ -280,11 +276,11 @@ int h2g_kate_division(const uint64_t* a, size_t len, const uint64_t b[4], uint64
 int h2g_multiopen_prove(uint64_t params, int scheme, uint64_t transcript, const h2g_poly_ref* polys, size_t npolys,
                         const h2g_open_query* queries, size_t nqueries) {
   NEED_DEV_P();
-  auto ip = g_params.find(params);
-  if (ip == g_params.end()) return fail(H2G_ERR_HANDLE, "unknown params");
+  Params* ip = find_params(params);
+  if (!ip) return fail(H2G_ERR_HANDLE, "unknown params");
   TranscriptObj* T = find_transcript(transcript);
   if (!T) return fail(H2G_ERR_HANDLE, "unknown transcript");
-  Params& prm = *ip->second;
+  Params& prm = *ip;
   if (prm.device != d->id) return fail(H2G_ERR_ARG, "multiopen_prove: params live on another device");
   if (scheme != MULTIOPEN_SHPLONK && scheme != MULTIOPEN_GWC)
     return fail(H2G_ERR_ARG, "multiopen_prove: scheme must be 0 (SHPLONK) or 1 (GWC)");
@@ -323,10 +319,7 @@ int h2g_multiopen_prove(uint64_t params, int scheme, uint64_t transcript, const 
     PALLOC(ws.pool, ws.q1, n);
     PALLOC(ws.pool, ws.scr, kate_scratch_len(n));
   }
-  if (nqueries + 1 > ws.small_len) {  // >= the points of a rotation set, the GWC point groups
-    PALLOC(ws.pool, ws.small, nqueries + 1);
-    ws.small_len = nqueries + 1;
-  }
+  HIPCHK(ws.small.ensure(nqueries + 1));
   // this call's own allocations: host polynomials brought to the device, the evaluations
   Pool call;
   MsmRingGuard ring_guard{d};
@@ -387,7 +380,7 @@ int h2g_multiopen_prove(uint64_t params, int scheme, uint64_t transcript, const 
   c.polys = &prs;
   c.queries = &qs;
   c.ev = [&](int poly, const Fr& pt) { return evals[index(poly, pt)]; };
-  c.nx = ws.nx, c.hx = ws.hx, c.lx = ws.lx, c.q1 = ws.q1, c.scr = ws.scr, c.small = ws.small;
+  c.nx = ws.nx, c.hx = ws.hx, c.lx = ws.lx, c.q1 = ws.q1, c.scr = ws.scr, c.small = ws.small.p;
   c.gwc_q = &ws.gwc_q;
   c.pool = &ws.pool;
   c.upload = [st](void* dst, const void* src, size_t bytes) {

@@ -58,20 +58,14 @@ int slab_carries(MultiopenCtx& c, const std::vector<Fr>& pts, Buf a, std::vector
   const uint64_t m = hq > sl.lo ? hq - sl.lo : 0;
   std::vector<EvalReq> reqs(np);
   for (size_t i = 0; i < np; i++) reqs[i] = EvalReq{a(i) + sl.lo + 1, m, pts[i]};
-  if ((int)np > pk.max_reqs) {
-    PALLOC(pk.pool, pk.d_reqs, np);
-    PALLOC(pk.pool, pk.evals, np);
-    pk.max_reqs = (int)np;
-  }
+  HIPCHK(pk.d_reqs.ensure(np));
+  HIPCHK(pk.evals.ensure(np));
   const size_t need = poly_eval_scratch_len((int)np, m ? m : 1);
-  if (need > pk.eval_scr_len) {
-    PALLOC(pk.pool, pk.eval_scr, need);
-    pk.eval_scr_len = need;
-  }
-  HIPCHK(c.upload(pk.d_reqs, reqs.data(), np * sizeof(EvalReq)));
-  HIPCHK(poly_eval_batch(pk.d_reqs, (int)np, m ? m : 1, pk.evals, pk.eval_scr, st));
+  HIPCHK(pk.eval_scr.ensure(need));
+  HIPCHK(c.upload(pk.d_reqs.p, reqs.data(), np * sizeof(EvalReq)));
+  HIPCHK(poly_eval_batch(pk.d_reqs.p, (int)np, m ? m : 1, pk.evals.p, pk.eval_scr.p, st));
   std::vector<Fr> mine(np);
-  HIPCHK(hipMemcpyAsync(mine.data(), pk.evals, np * sizeof(Fr), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(mine.data(), pk.evals.p, np * sizeof(Fr), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   std::vector<Fr> all;
   RCCHK(spmd_allgather_fr(mine, &all));
@@ -262,11 +256,8 @@ int multiopen_shplonk(MultiopenCtx& c) {
     }
     // slab mode: per point a (slab + halo) buffer; gbuf(i) indexes it globally
     const size_t np = super_pts.size(), cap = sl.hi1 - sl.lo + 1;
-    if (slabs && np * cap > c.slab_pk->slab_buf_len) {
-      PALLOC(c.slab_pk->pool, c.slab_pk->slab_buf, np * cap);
-      c.slab_pk->slab_buf_len = np * cap;
-    }
-    auto gbuf = [&](size_t i) { return c.slab_pk->slab_buf + i * cap - sl.lo; };
+    if (slabs) HIPCHK(c.slab_pk->slab_buf.ensure(np * cap));
+    auto gbuf = [&](size_t i) { return c.slab_pk->slab_buf.p + i * cap - sl.lo; };
     if (slabs) HIPCHK(hipMemsetAsync(c.hx + sl.lo, 0, (sl.hi1 - sl.lo) * sizeof(Fr), st));
     else HIPCHK(hipMemsetAsync(c.hx, 0, n * sizeof(Fr), st));
     for (size_t pi = 0; pi < np; pi++) {

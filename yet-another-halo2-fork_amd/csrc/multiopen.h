@@ -116,6 +116,7 @@ struct TranscriptObj {
   bool read_scalar(Fr* out);
 };
 extern std::map<uint64_t, std::unique_ptr<TranscriptObj>> g_transcripts;  // kzg.cpp
+inline TranscriptObj* find_transcript(uint64_t h) { return find_handle(g_transcripts, h); }
 
 }  // namespace prv
 }  // namespace h2g

@@ -152,9 +152,9 @@ int h2g_params_from_parts(uint32_t k, const uint64_t* g, const uint64_t* g_lagra
 int h2g_params_downsize(uint64_t params, uint32_t k, uint64_t* handle) {
   NEED_DEV_P();
   if (!handle) return fail(H2G_ERR_ARG, "params_downsize: null handle output");
-  auto it = g_params.find(params);
-  if (it == g_params.end()) return fail(H2G_ERR_HANDLE, "unknown params");
-  const Params& src = *it->second;
+  Params* it = find_params(params);
+  if (!it) return fail(H2G_ERR_HANDLE, "unknown params");
+  const Params& src = *it;
   if (src.device != d->id) return fail(H2G_ERR_ARG, "params_downsize: params live on another device");
   if (k > src.k || k > G1FFT_MAX_K)
     return fail(H2G_ERR_ARG, "params_downsize: k = " + std::to_string(k) + " above the params' " + std::to_string(src.k));
@@ -178,10 +178,10 @@ int h2g_params_downsize(uint64_t params, uint32_t k, uint64_t* handle) {
 
 int h2g_params_export(uint64_t params, uint64_t* g, uint64_t* g_lagrange) {
   NEED_DEV_P();
-  auto it = g_params.find(params);
-  if (it == g_params.end()) return fail(H2G_ERR_HANDLE, "unknown params");
-  if (g) HIPCHK(hipMemcpy(g, it->second->g, it->second->n * sizeof(G1Affine), hipMemcpyDeviceToHost));
-  if (g_lagrange) HIPCHK(hipMemcpy(g_lagrange, it->second->gl, it->second->n * sizeof(G1Affine), hipMemcpyDeviceToHost));
+  Params* it = find_params(params);
+  if (!it) return fail(H2G_ERR_HANDLE, "unknown params");
+  if (g) HIPCHK(hipMemcpy(g, it->g, it->n * sizeof(G1Affine), hipMemcpyDeviceToHost));
+  if (g_lagrange) HIPCHK(hipMemcpy(g_lagrange, it->gl, it->n * sizeof(G1Affine), hipMemcpyDeviceToHost));
   return H2G_OK;
 }
 
@@ -194,33 +194,33 @@ int h2g_params_free(uint64_t params) {
 /* the G2 points of the params: 16 u64 each (x.c0, x.c1, y.c0, y.c1, Montgomery) */
 int h2g_params_g2(uint64_t params, uint64_t g2[16], uint64_t s_g2[16]) {
   NEED_DEV_P();
-  auto it = g_params.find(params);
-  if (it == g_params.end()) return fail(H2G_ERR_HANDLE, "unknown params");
-  if (!it->second->has_g2) return fail(H2G_ERR_STATE, "params have no G2 points");
-  if (g2) std::memcpy(g2, &it->second->g2, sizeof(G2Affine));
-  if (s_g2) std::memcpy(s_g2, &it->second->s_g2, sizeof(G2Affine));
+  Params* it = find_params(params);
+  if (!it) return fail(H2G_ERR_HANDLE, "unknown params");
+  if (!it->has_g2) return fail(H2G_ERR_STATE, "params have no G2 points");
+  if (g2) std::memcpy(g2, &it->g2, sizeof(G2Affine));
+  if (s_g2) std::memcpy(s_g2, &it->s_g2, sizeof(G2Affine));
   return H2G_OK;
 }
 int h2g_params_set_g2(uint64_t params, const uint64_t g2[16], const uint64_t s_g2[16]) {
   NEED_DEV_P();
-  auto it = g_params.find(params);
-  if (it == g_params.end()) return fail(H2G_ERR_HANDLE, "unknown params");
+  Params* it = find_params(params);
+  if (!it) return fail(H2G_ERR_HANDLE, "unknown params");
   if (!g2 || !s_g2) return fail(H2G_ERR_ARG, "params_set_g2: null argument");
   G2Affine a, b;
   std::memcpy(&a, g2, sizeof(G2Affine));
   std::memcpy(&b, s_g2, sizeof(G2Affine));
   if (!g2_valid(a) || !g2_valid(b)) return fail(H2G_ERR_ARG, "params_set_g2: invalid G2 point");
-  it->second->g2 = a;
-  it->second->s_g2 = b;
-  it->second->has_g2 = true;
+  it->g2 = a;
+  it->s_g2 = b;
+  it->has_g2 = true;
   return H2G_OK;
 }
 
 int h2g_params_set_slab(uint64_t params, uint64_t lo, uint64_t hi) {
   NEED_DEV_P();
-  auto ip = g_params.find(params);
-  if (ip == g_params.end()) return fail(H2G_ERR_HANDLE, "unknown params");
-  Params& prm = *ip->second;
+  Params* ip = find_params(params);
+  if (!ip) return fail(H2G_ERR_HANDLE, "unknown params");
+  Params& prm = *ip;
   if (prm.device != d->id) return fail(H2G_ERR_ARG, "params_set_slab: params live on another device");
   if (lo > hi || hi > prm.n) return fail(H2G_ERR_ARG, "params_set_slab: bad range");
   msm_fixed_base_free(&prm.sg);
@@ -240,10 +240,10 @@ int h2g_params_set_slab(uint64_t params, uint64_t lo, uint64_t hi) {
 
 int h2g_params_table_bytes(uint64_t params, uint64_t out[4]) {
   std::lock_guard<std::recursive_mutex> lk(g_mu);
-  auto ip = g_params.find(params);
-  if (ip == g_params.end()) return fail(H2G_ERR_HANDLE, "unknown params");
+  Params* ip = find_params(params);
+  if (!ip) return fail(H2G_ERR_HANDLE, "unknown params");
   if (!out) return fail(H2G_ERR_ARG, "params_table_bytes: null output");
-  const Params& p = *ip->second;
+  const Params& p = *ip;
   auto bytes = [](const MsmFixedBase& t) -> uint64_t {
     return t.table ? (uint64_t)t.W * (uint64_t)t.n * sizeof(G1Affine) : 0;
   };
@@ -257,9 +257,9 @@ int h2g_params_table_bytes(uint64_t params, uint64_t out[4]) {
 int h2g_params_msm_dev(uint64_t params, int32_t base_set, uint64_t offset, uint64_t n, const void* d_scalars,
                        uint64_t out_affine[8], int32_t* out_is_identity) {
   NEED_DEV_P();
-  auto ip = g_params.find(params);
-  if (ip == g_params.end()) return fail(H2G_ERR_HANDLE, "unknown params");
-  Params& prm = *ip->second;
+  Params* ip = find_params(params);
+  if (!ip) return fail(H2G_ERR_HANDLE, "unknown params");
+  Params& prm = *ip;
   if (prm.device != d->id) return fail(H2G_ERR_ARG, "params_msm_dev: params live on another device");
   if (base_set < SRS_G || base_set > SRS_LAGRANGE_PREFIX || offset > prm.n || n > prm.n - offset || !out_affine ||
       (n && !d_scalars))

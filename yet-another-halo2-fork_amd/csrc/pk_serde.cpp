@@ -243,14 +243,14 @@ extern "C" {
 /* VerifyingKey::write / read (plonk.rs:73-129): the prefix of h2g_pk_write's bytes */
 int h2g_vk_write(uint64_t vk, int format, uint8_t* out, size_t cap, size_t* len) {
   std::lock_guard<std::recursive_mutex> lk(g_mu);
-  auto it = g_vks.find(vk);
-  if (it == g_vks.end()) return fail(H2G_ERR_HANDLE, "unknown verifying key");
+  VerifyingKey* it = find_vk(vk);
+  if (!it) return fail(H2G_ERR_HANDLE, "unknown verifying key");
   if (!len) return fail(H2G_ERR_ARG, "vk_write: null length");
   if (format != SERDE_RAW && format != SERDE_RAW_UNCHECKED && format != SERDE_PROCESSED)
     return fail(H2G_ERR_ARG, "vk_write: unknown SerdeFormat");
   ByteWriter w{out, out ? cap : 0, nullptr};
   w.proc = format == SERDE_PROCESSED;
-  vk_write_prefix(w, it->second->cs.k, it->second->fixed, it->second->perm);
+  vk_write_prefix(w, it->cs.k, it->fixed, it->perm);
   *len = w.len;
   if (out && w.len > cap) return fail(H2G_ERR_ARG, "vk_write: buffer too small");
   return H2G_OK;
@@ -274,12 +274,12 @@ int h2g_vk_read(const h2g_circuit* circuit, const uint8_t* buf, size_t len, int 
 /* ParamsKZG::write_custom (kzg/commitment.rs:166-181): k (u32 LE), g, g_lagrange, g2, s_g2 */
 int h2g_params_write(uint64_t params, int format, uint8_t* out, size_t cap, size_t* len) {
   NEED_DEV_P();
-  auto it = g_params.find(params);
-  if (it == g_params.end()) return fail(H2G_ERR_HANDLE, "unknown params");
+  Params* it = find_params(params);
+  if (!it) return fail(H2G_ERR_HANDLE, "unknown params");
   if (!len) return fail(H2G_ERR_ARG, "params_write: null length");
   if (format != SERDE_RAW && format != SERDE_RAW_UNCHECKED && format != SERDE_PROCESSED)
     return fail(H2G_ERR_ARG, "params_write: unknown SerdeFormat");
-  const Params& p = *it->second;
+  const Params& p = *it;
   if (!p.has_g2) return fail(H2G_ERR_STATE, "params_write: the params have no G2 points (h2g_params_set_g2)");
   ByteWriter w{out, out ? cap : 0, d->stream};
   w.proc = format == SERDE_PROCESSED;
@@ -361,19 +361,19 @@ int h2g_params_read(const uint8_t* buf, size_t len, int format, uint64_t* handle
 /* ProvingKey::write (plonk.rs:311-321) with VerifyingKey::write (plonk.rs:73-86) */
 int h2g_pk_write(uint64_t pk_h, int format, uint8_t* out, size_t cap, size_t* len) {
   NEED_DEV_P();
-  auto it = g_pks.find(pk_h);
-  if (it == g_pks.end()) return fail(H2G_ERR_HANDLE, "unknown proving key");
+  ProvingKey* it = find_pk(pk_h);
+  if (!it) return fail(H2G_ERR_HANDLE, "unknown proving key");
   if (!len) return fail(H2G_ERR_ARG, "pk_write: null length");
   if (format != SERDE_RAW && format != SERDE_RAW_UNCHECKED && format != SERDE_PROCESSED)
     return fail(H2G_ERR_ARG, "pk_write: unknown SerdeFormat");
-  ProvingKey& pk = *it->second;
-  auto pit = g_params.find(pk.params);
-  if (pit == g_params.end()) return fail(H2G_ERR_HANDLE, "pk_write: the key's params were freed");
+  ProvingKey& pk = *it;
+  Params* pit = find_params(pk.params);
+  if (!pit) return fail(H2G_ERR_HANDLE, "pk_write: the key's params were freed");
   RCCHK(h2g_pk_vk_commitments(pk_h, nullptr, nullptr));  // commit_lagrange, once
   HIPCHK(hipStreamSynchronize(d->stream));
   ByteWriter w{out, out ? cap : 0, d->stream};
   w.proc = format == SERDE_PROCESSED;
-  vk_write_prefix(w, pk.k, pk.vk_fixed, pk.vk_perm);
+  vk_write_prefix(w, pk.cs.k, pk.vk_fixed, pk.vk_perm);
   RCCHK(w.poly(pk.l0, pk.ext));
   RCCHK(w.poly(pk.l_last, pk.ext));
   RCCHK(w.poly(pk.l_active, pk.ext));
@@ -394,15 +394,15 @@ int h2g_pk_write(uint64_t pk_h, int format, uint8_t* out, size_t cap, size_t* le
 int h2g_pk_read(uint64_t params, const h2g_circuit* circuit, const uint8_t* buf, size_t len, int format,
                 uint64_t* pk_out) {
   NEED_DEV_P();
-  auto it = g_params.find(params);
-  if (it == g_params.end()) return fail(H2G_ERR_HANDLE, "unknown params");
+  Params* it = find_params(params);
+  if (!it) return fail(H2G_ERR_HANDLE, "unknown params");
   if (!circuit || !buf || !pk_out) return fail(H2G_ERR_ARG, "pk_read: null argument");
   if (format != SERDE_RAW && format != SERDE_RAW_UNCHECKED && format != SERDE_PROCESSED)
     return fail(H2G_ERR_ARG, "pk_read: unknown SerdeFormat");
   const bool proc = format == SERDE_PROCESSED;
   ByteReader r{buf, len};
   const uint32_t k = circuit->k, F = circuit->num_fixed, P = circuit->num_perm_columns;
-  if (k != it->second->k) return fail(H2G_ERR_ARG, "pk_read: k does not match");
+  if (k != it->k) return fail(H2G_ERR_ARG, "pk_read: k does not match");
   std::vector<G1Affine> vf, vp;
   RCCHK(vk_read_prefix(r, format, circuit, "pk_read", &vf, &vp));
   // the extended domain size follows from the constraint system (keygen::create_domain):
@@ -435,7 +435,7 @@ int h2g_pk_read(uint64_t params, const h2g_circuit* circuit, const uint8_t* buf,
   }
   auto pk = std::make_unique<ProvingKey>();
   pk->params = params;
-  int rc = keygen_impl(d, *it->second, circuit, *pk, &img);
+  int rc = keygen_impl(d, *it, circuit, *pk, &img);
   if (rc == H2G_OK && proc) {
     uint32_t nbad = 0;
     if (hipMemcpyAsync(&nbad, bad.p, 4, hipMemcpyDeviceToHost, d->stream) != hipSuccess ||
@@ -446,12 +446,12 @@ int h2g_pk_read(uint64_t params, const h2g_circuit* circuit, const uint8_t* buf,
   if (rc == H2G_OK && pk->ext != ext_len) rc = fail(H2G_ERR_ARG, "pk_read: extended domain size does not match the circuit");
   if (rc == H2G_OK && format == SERDE_RAW) {
     std::vector<std::pair<const Fr*, size_t>> arrays = {{pk->l0, pk->ext}, {pk->l_last, pk->ext}, {pk->l_active, pk->ext}};
-    for (int i = 0; i < pk->F; i++) {
+    for (int i = 0; i < pk->cs.F; i++) {
       arrays.push_back({pk->fixed_lag[i], n});
       arrays.push_back({pk->fixed_poly[i], n});
       arrays.push_back({pk->fixed_coset[i], pk->ext});
     }
-    for (int i = 0; i < pk->P; i++) {
+    for (int i = 0; i < pk->cs.P; i++) {
       arrays.push_back({pk->sigma_lag[i], n});
       arrays.push_back({pk->sigma_poly[i], n});
       arrays.push_back({pk->sigma_coset[i], pk->ext});
@@ -460,10 +460,7 @@ int h2g_pk_read(uint64_t params, const h2g_circuit* circuit, const uint8_t* buf,
     rc = count_bad_fr(arrays, d->stream, &nbad);
     if (rc == H2G_OK && nbad) rc = fail(H2G_ERR_ARG, "pk_read: " + std::to_string(nbad) + " field elements not below the modulus");
   }
-  if (rc) {
-    domain_release(&pk->dom);
-    return rc;
-  }
+  if (rc) return rc;
   pk->vk_fixed = vf;
   pk->vk_perm = vp;
   *pk_out = g_next_handle++;

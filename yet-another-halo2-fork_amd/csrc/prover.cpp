@@ -71,11 +71,7 @@ struct StageClock {
 // stream, so no copy of the previous proof still reads it
 int pk_upload_arm(ProvingKey& pk, hipStream_t st) {
   HIPCHK(hipStreamSynchronize(st));
-  if (!pk.up_h) {
-    constexpr size_t kLen = 4u << 20;
-    HIPCHK(hipHostMalloc((void**)&pk.up_h, kLen, hipHostMallocDefault));
-    pk.up_len = kLen;
-  }
+  HIPCHK(pk.up_h.ensure(4u << 20));
   pk.up_off = 0;
   return H2G_OK;
 }
@@ -86,42 +82,35 @@ namespace h2g {
 namespace prv {
 hipError_t pk_upload(ProvingKey& pk, void* dst, const void* src, size_t bytes, hipStream_t st) {
   const size_t a = (pk.up_off + 63) & ~(size_t)63;
-  if (pk.up_h && a + bytes <= pk.up_len) {
-    std::memcpy(pk.up_h + a, src, bytes);
+  if (a + bytes <= pk.up_h.len) {
+    std::memcpy(pk.up_h.p + a, src, bytes);
     pk.up_off = a + bytes;
-    return hipMemcpyAsync(dst, pk.up_h + a, bytes, hipMemcpyHostToDevice, st);
+    return hipMemcpyAsync(dst, pk.up_h.p + a, bytes, hipMemcpyHostToDevice, st);
   }
   return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st);
+}
+int copy_list_run(ProvingKey& pk, const std::vector<CopySeg>& segs, hipStream_t st) {
+  if (segs.empty()) return H2G_OK;
+  HIPCHK(pk.d_segs.ensure(segs.size()));
+  uint64_t mx = 0;
+  for (const CopySeg& g : segs) mx = std::max<uint64_t>(mx, g.len);
+  HIPCHK(pk_upload(pk, pk.d_segs.p, segs.data(), segs.size() * sizeof(CopySeg), st));
+  HIPCHK(copy_segments(pk.d_segs.p, (int)segs.size(), mx, st));
+  return H2G_OK;
 }
 }  // namespace prv
 }  // namespace h2g
 
 namespace {
 
-// device staging for a batch of blinding rows (grow-only)
-int blind_stage(ProvingKey& pk, size_t count) {
-  if (count > pk.blind_d_len) {
-    PALLOC(pk.pool, pk.blind_d, count);
-    pk.blind_d_len = count;
-  }
-  return H2G_OK;
-}
 // several blocks of blinding rows in one upload and one copy launch: `host` (count Fr) lands
-// in pk.blind_d, which `segs` read from.  Every small host-to-device copy is a ~6-us blit
+// in pk.blind_d.p (sized by the caller, before it built `segs`), which `segs` read from.  Every small host-to-device copy is a ~6-us blit
 // on the stream; a keccak-style proof made ~80 of them, one per column and lookup side
 int upload_rows_batch(ProvingKey& pk, const Fr* host, size_t count, const std::vector<CopySeg>& segs,
                       hipStream_t st) {
   if (segs.empty()) return H2G_OK;
-  HIPCHK(pk_upload(pk, pk.blind_d, host, count * sizeof(Fr), st));
-  if (segs.size() > pk.d_segs_len) {
-    PALLOC(pk.pool, pk.d_segs, segs.size());
-    pk.d_segs_len = segs.size();
-  }
-  uint64_t mx = 0;
-  for (const CopySeg& g : segs) mx = std::max<uint64_t>(mx, g.len);
-  HIPCHK(pk_upload(pk, pk.d_segs, segs.data(), segs.size() * sizeof(CopySeg), st));
-  HIPCHK(copy_segments(pk.d_segs, (int)segs.size(), mx, st));
-  return H2G_OK;
+  HIPCHK(pk_upload(pk, pk.blind_d.p, host, count * sizeof(Fr), st));
+  return copy_list_run(pk, segs, st);
 }
 
 
@@ -153,7 +142,7 @@ struct ProofRun {
   std::vector<uint8_t>* const proof;
   const hipStream_t st = d->stream;
   const size_t n = pk.n, ext = pk.ext;
-  const int bf = pk.bf;
+  const int bf = pk.cs.bf;
   const Domain& D = pk.dom;
   const int ncirc = in.nc;
   std::vector<CircuitWs*> W = std::vector<CircuitWs*>(ncirc);
@@ -245,7 +234,7 @@ struct ProofRun {
   // not sub-coset leaders: C3 at 8 ranks has 3 advice + 3 grand products for 6 ranks; at 4
   // ranks two transforms would share a rank in the permutation stage, measured slower:
   // profiles/r05/emulation/defer_adv/)
-  const int n_xf = ncirc * (pk.A + pk.nsets + 3 * pk.NL + pk.NS);
+  const int n_xf = ncirc * (pk.cs.A + pk.cs.nsets + 3 * pk.cs.NL + pk.cs.NS);
   const bool defer_adv = pieces && n_xf <= Wsp - E_sub;
   void xform_later(const std::vector<const Fr*>& lag, const std::vector<Fr*>& pol, const std::vector<Fr*>& cst) {
     DeferredXform x{lag, pol, cst, std::vector<int>(lag.size())};
@@ -277,9 +266,9 @@ struct ProofRun {
   const size_t unusable = n - (size_t)(bf + 1);
   // host staging that device copies read asynchronously: lives until the proof returns
   // (every copy has completed by then: the final commitment is collected after it)
-  std::vector<Fr> adv_blind = std::vector<Fr>((size_t)ncirc * pk.A * (bf + 1));
+  std::vector<Fr> adv_blind = std::vector<Fr>((size_t)ncirc * pk.cs.A * (bf + 1));
   const bool from_src = in.src || in.src1;
-  const int NCH = (int)pk.ch_phase.size();
+  const int NCH = (int)pk.cs.ch_phase.size();
   std::vector<Fr> challenges = std::vector<Fr>(NCH);
   StreamSyncGuard adv_guard{st};
   // the vanishing argument's seeds and chunk offsets (staging read by async copies: lives
@@ -306,15 +295,15 @@ struct ProofRun {
     // vanishing stage checks that the real draws equal these bytes (else it redoes both)
     van_seeds.assign(van_off.size() * 8, 0);
     rng.peek((uint64_t)pk.van_pos, reinterpret_cast<uint8_t*>(van_seeds.data()), van_seeds.size() * 4);
-    HIPCHK(pk_upload(pk, pk.d_seeds, van_seeds.data(), van_seeds.size() * 4, st));
-    HIPCHK(pk_upload(pk, pk.d_offsets, van_off.data(), van_off.size() * 8, st));
-    HIPCHK(chacha_random_poly(pk.random_poly, n, pk.d_seeds, pk.d_offsets, (int)van_off.size(), st, sl.lo, sl.hi1));
+    HIPCHK(pk_upload(pk, pk.d_seeds.p, van_seeds.data(), van_seeds.size() * 4, st));
+    HIPCHK(pk_upload(pk, pk.d_offsets.p, van_off.data(), van_off.size() * 8, st));
+    HIPCHK(chacha_random_poly(pk.random_poly, n, pk.d_seeds.p, pk.d_offsets.p, (int)van_off.size(), st, sl.lo, sl.hi1));
     RCCHK(commit_launch(d, prm, pk.random_poly, n, SRS_G, st, &van_tk));
     van_early = true;
     return H2G_OK;
   }
   // advice columns distributed by their owners
-  std::vector<char> adv_shard = std::vector<char>((size_t)ncirc * pk.A, 0);
+  std::vector<char> adv_shard = std::vector<char>((size_t)ncirc * pk.cs.A, 0);
   // advice handed over in host memory: the first column's upload has nothing to overlap
   // (its MSM needs the whole column), so the random polynomial's commitment goes first and
   // runs under that upload; device-resident advice keeps it behind the advice commitments
@@ -343,23 +332,23 @@ struct ProofRun {
     HIPCHK(compress_lagrange(ca, st));
     return H2G_OK;
   }
-  const int NLT = ncirc * pk.NL;  // (circuit, lookup) pairs, circuit-major: j = ci * NL + l
+  const int NLT = ncirc * pk.cs.NL;  // (circuit, lookup) pairs, circuit-major: j = ci * NL + l
   bool lk_shard = false;  // the lookups went to their owners (A', S' and z distributed)
   std::vector<int> lk_owner_all = std::vector<int>(NLT, g_spmd.rank);
-  const int NST = ncirc * pk.nsets;  // (circuit, set), circuit-major
+  const int NST = ncirc * pk.cs.nsets;  // (circuit, set), circuit-major
   std::vector<MsmTicket> perm_tk = std::vector<MsmTicket>(NST);
   // host staging of every set's / product's blinding rows: no host synchronisation per
   // set, the transforms of all sets go as batches after the loop
   std::vector<Fr> perm_blind = std::vector<Fr>((size_t)NST * bf),
-                  prod_blind = std::vector<Fr>((size_t)ncirc * (pk.NL + pk.NS) * bf);
+                  prod_blind = std::vector<Fr>((size_t)ncirc * (pk.cs.NL + pk.cs.NS) * bf);
   StreamSyncGuard blind_guard{st};
   std::vector<Fr*> all_z_lag, all_z, all_z_coset;
   const Fr* col_vals(const CircuitWs& w, int c) const {
-    const auto& pc = pk.perm_cols[c];
+    const auto& pc = pk.cs.perm_cols[c];
     return pc.first == COL_ADVICE ? w.adv[pc.second]
                                   : (pc.first == COL_FIXED ? pk.fixed_lag[pc.second] : w.inst_val[pc.second]);
   }
-  const int NSH = ncirc * pk.NS;
+  const int NSH = ncirc * pk.cs.NS;
   std::vector<MsmTicket> lkz_tk = std::vector<MsmTicket>(NLT), shz_tk = std::vector<MsmTicket>(NSH);
   // the evaluate_h arguments that depend neither on the domain (whole cosets or one
   // sub-coset) and the output nor on the sub-coset's slot: the caller fills those
@@ -369,13 +358,13 @@ struct ProofRun {
     a.gates = pk.seg_gates;
     a.n_slots = pk.n_slots;
     a.theta = theta;
-    a.nlookups = pk.NL;
-    a.nshuffles = pk.NS;
+    a.nlookups = pk.cs.NL;
+    a.nshuffles = pk.cs.NS;
     a.consts = pk.consts;
     a.query_rot = pk.d_load_rot;
-    a.nsets = pk.nsets;
-    a.chunk_len = pk.chunk_len;
-    a.P = pk.P;
+    a.nsets = pk.cs.nsets;
+    a.chunk_len = pk.cs.chunk_len;
+    a.P = pk.cs.P;
     a.beta = beta;
     a.gamma = gamma;
     a.y = y;
@@ -387,11 +376,11 @@ struct ProofRun {
 
   // poly ids: per circuit ci (base ci * per_c): advice c, z s, lookup l (z, A', S'),
   // shuffle s; then fixed, sigma, h, random
-  const int per_c = pk.A + pk.nsets + 3 * pk.NL + pk.NS;
+  const int per_c = pk.cs.A + pk.cs.nsets + 3 * pk.cs.NL + pk.cs.NS;
   int id_adv(int ci) const { return ci * per_c; }
-  int id_z(int ci) const { return ci * per_c + pk.A; }
-  int id_lk(int ci) const { return ci * per_c + pk.A + pk.nsets; }  // lookup l: z, A', S' at + 3 l
-  int id_sh(int ci) const { return ci * per_c + pk.A + pk.nsets + 3 * pk.NL; }
+  int id_z(int ci) const { return ci * per_c + pk.cs.A; }
+  int id_lk(int ci) const { return ci * per_c + pk.cs.A + pk.cs.nsets; }  // lookup l: z, A', S' at + 3 l
+  int id_sh(int ci) const { return ci * per_c + pk.cs.A + pk.cs.nsets + 3 * pk.cs.NL; }
   std::vector<PolyRef> polys;
   std::vector<OpenQ> queries;
   // unique (poly, point) evaluations, one batched launch
@@ -420,13 +409,13 @@ struct ProofRun {
   }
   int msm_ring_peak() const {
     int peak_msms = 0;
-    for (int ph = 0; ph <= pk.max_phase; ph++) {
+    for (int ph = 0; ph <= pk.cs.max_phase; ph++) {
       int a = 0;
-      for (int c = 0; c < pk.A; c++) a += pk.adv_phase[c] == ph;
+      for (int c = 0; c < pk.cs.A; c++) a += pk.cs.adv_phase[c] == ph;
       peak_msms = std::max(peak_msms, a * ncirc);
     }
-    peak_msms = std::max(peak_msms, 2 * ncirc * pk.NL);
-    peak_msms = std::max(peak_msms, ncirc * (pk.nsets + pk.NL + pk.NS));
+    peak_msms = std::max(peak_msms, 2 * ncirc * pk.cs.NL);
+    peak_msms = std::max(peak_msms, ncirc * (pk.cs.nsets + pk.cs.NL + pk.cs.NS));
     return peak_msms;
   }
 
@@ -452,9 +441,9 @@ struct ProofRun {
 
 // ---- vk.hash_into + every circuit's instances (prover.rs:187-271; KZG: QUERY_INSTANCE = false)
 int ProofRun::instances() {
-  tr.common_scalar(pk.transcript_repr);
+  tr.common_scalar(pk.cs.transcript_repr);
   for (int ci = 0; ci < ncirc; ci++)
-    for (int i = 0; i < pk.I; i++) {
+    for (int i = 0; i < pk.cs.I; i++) {
       const uint32_t len = in.inst_lens[ci][i];
       if ((size_t)len > n - (size_t)(bf + 1)) return fail(H2G_ERR_ARG, "create_proof: InstanceTooLarge");
       const uint64_t* col = in.instance[ci] + 4 * n * i;
@@ -471,7 +460,7 @@ int ProofRun::advice_phases() {
   if (from_src)  // a witness source writes straight into pinned staging, one per circuit,
     for (CircuitWs* w : W) {  // allocated once (a pinned allocation costs more than the copies it speeds up)
       if (w->wit_pin) continue;
-      const size_t bytes = (size_t)std::max(pk.A, 1) * n * sizeof(Fr);
+      const size_t bytes = (size_t)std::max(pk.cs.A, 1) * n * sizeof(Fr);
       if (hipHostMalloc((void**)&w->wit_pin, bytes, hipHostMallocDefault) == hipSuccess) {
         w->wit_pin_pinned = true;
       } else {  // pageable fallback: slower uploads, same bytes
@@ -481,16 +470,13 @@ int ProofRun::advice_phases() {
         if (!w->wit_pin) return fail(H2G_ERR_NOMEM, "create_proof: witness staging allocation failed");
       }
     }
-  if ((int)van_off.size() > pk.max_chunks) {
-    PALLOC(pk.pool, pk.d_seeds, van_off.size() * 8);
-    PALLOC(pk.pool, pk.d_offsets, van_off.size());
-    pk.max_chunks = (int)van_off.size();
-  }
-  for (int ph = 0; ph <= pk.max_phase; ph++) {
+  HIPCHK(pk.d_seeds.ensure(van_off.size() * 8));
+  HIPCHK(pk.d_offsets.ensure(van_off.size()));
+  for (int ph = 0; ph <= pk.cs.max_phase; ph++) {
     if (ph == 0 && van_first) RCCHK(launch_van_early());
     std::vector<int> cols;
-    for (int c = 0; c < pk.A; c++)
-      if (pk.adv_phase[c] == ph) cols.push_back(c);
+    for (int c = 0; c < pk.cs.A; c++)
+      if (pk.cs.adv_phase[c] == ph) cols.push_back(c);
     if (from_src && ph > 0) HIPCHK(hipStreamSynchronize(st));  // the previous phase's uploads read the staging
     std::vector<MsmTicket> tk(cols.size() * ncirc);
     // a wide phase: column i (circuit-major) is rank i mod world's -- every rank uploads the
@@ -539,7 +525,7 @@ int ProofRun::advice_phases() {
       };
       auto blind = [&](int c) -> int {
         if (pk.unblinded[c]) return H2G_OK;
-        Fr* rows = adv_blind.data() + ((size_t)ci * pk.A + c) * (bf + 1);
+        Fr* rows = adv_blind.data() + ((size_t)ci * pk.cs.A + c) * (bf + 1);
         for (int i = 0; i <= bf; i++) rows[i] = rng.random_fr();
         HIPCHK(pk_upload(pk, w.adv[c] + unusable, rows, (size_t)(bf + 1) * sizeof(Fr), st));
         return H2G_OK;
@@ -547,7 +533,7 @@ int ProofRun::advice_phases() {
       for (size_t k = 0; k < cols.size(); k++) {
         const int c = cols[k];
         const Fr* src = reinterpret_cast<const Fr*>(from + 4 * n * c);
-        unsigned long long* sum = digest ? pk.wsum_d + (size_t)ci * cols.size() + k : nullptr;
+        unsigned long long* sum = digest ? pk.wsum_d.p + (size_t)ci * cols.size() + k : nullptr;
         if (from_dev) {
           cc.src[ncc] = src;
           cc.dst[ncc] = w.adv[c];
@@ -568,15 +554,15 @@ int ProofRun::advice_phases() {
       }
       RCCHK(flush());
       if (!early) {  // every column's rows drawn in order, then one upload for the phase
-        RCCHK(blind_stage(pk, (size_t)pk.A * (bf + 1)));
+        HIPCHK(pk.blind_d.ensure((size_t)pk.cs.A * (bf + 1)));
         std::vector<CopySeg> segs;
         for (int c : cols) {
           if (pk.unblinded[c]) continue;
-          Fr* rows = adv_blind.data() + ((size_t)ci * pk.A + c) * (bf + 1);
+          Fr* rows = adv_blind.data() + ((size_t)ci * pk.cs.A + c) * (bf + 1);
           for (int i = 0; i <= bf; i++) rows[i] = rng.random_fr();
-          segs.push_back(CopySeg{pk.blind_d + (size_t)c * (bf + 1), w.adv[c] + unusable, (uint64_t)(bf + 1)});
+          segs.push_back(CopySeg{pk.blind_d.p + (size_t)c * (bf + 1), w.adv[c] + unusable, (uint64_t)(bf + 1)});
         }
-        RCCHK(upload_rows_batch(pk, adv_blind.data() + (size_t)ci * pk.A * (bf + 1), (size_t)pk.A * (bf + 1), segs,
+        RCCHK(upload_rows_batch(pk, adv_blind.data() + (size_t)ci * pk.cs.A * (bf + 1), (size_t)pk.cs.A * (bf + 1), segs,
                                 st));
       }
       for (int c : cols)
@@ -637,7 +623,7 @@ int ProofRun::advice_phases() {
     if (adv_wide) {
       RCCHK(xform(adv_lag, adv_poly, adv_cst, &adv_owner));
       for (int ci = 0; ci < ncirc; ci++)
-        for (int c : cols) adv_shard[(size_t)ci * pk.A + c] = 1;
+        for (int c : cols) adv_shard[(size_t)ci * pk.cs.A + c] = 1;
     }
     if (ph == 0 && early_van && !van_first) RCCHK(launch_van_early());
     if (ph == 0) clk.mark("upload+instances");
@@ -648,7 +634,7 @@ int ProofRun::advice_phases() {
     }
     RCCHK(rng_ok());
     for (int i = 0; i < NCH; i++)
-      if (pk.ch_phase[i] == ph) challenges[i] = tr.squeeze();
+      if (pk.cs.ch_phase[i] == ph) challenges[i] = tr.squeeze();
   }
   if (NCH)
     HIPCHK(pk_upload(pk, pk.consts + pk.num_consts, challenges.data(), NCH * sizeof(Fr), st));
@@ -668,25 +654,12 @@ int ProofRun::lookup_permuted() {
     // checked once all lookups are queued
     std::vector<Fr> rows((size_t)NLT * 2 * (bf + 1));
     constexpr int LKC = ProvingKey::LKC;
-    if ((size_t)NLT * LKC > pk.lk_cnt_len) {
-      if (pk.lk_cnt) (void)hipHostFree(pk.lk_cnt);
-      pk.lk_cnt = nullptr;
-      pk.lk_cnt_len = 0;
-      HIPCHK(hipHostMalloc((void**)&pk.lk_cnt, (size_t)NLT * LKC * sizeof(uint32_t), hipHostMallocDefault));
-      pk.lk_cnt_len = (size_t)NLT * LKC;
-    }
     constexpr int LKF = ProvingKey::LKF;
-    if ((size_t)NLT > pk.lk_or_len) {
-      if (pk.lk_or_d) (void)hipFree(pk.lk_or_d);
-      if (pk.lk_or_h) (void)hipHostFree(pk.lk_or_h);
-      pk.lk_or_d = pk.lk_or_h = nullptr;
-      pk.lk_or_len = 0;
-      HIPCHK(hipMalloc((void**)&pk.lk_or_d, (size_t)NLT * LKF * sizeof(unsigned long long)));
-      HIPCHK(hipHostMalloc((void**)&pk.lk_or_h, (size_t)NLT * LKF * sizeof(unsigned long long), hipHostMallocDefault));
-      pk.lk_or_len = (size_t)NLT;
-    }
+    HIPCHK(pk.lk_cnt.ensure((size_t)NLT * LKC));
+    HIPCHK(pk.lk_or_d.ensure((size_t)NLT * LKF));
+    HIPCHK(pk.lk_or_h.ensure((size_t)NLT * LKF));
     if ((int)pk.lk_hb.size() < NLT) pk.lk_hb.resize(NLT, 64);
-    if (NLT) HIPCHK(hipMemsetAsync(pk.lk_or_d, 0, (size_t)NLT * LKF * sizeof(unsigned long long), st));
+    if (NLT) HIPCHK(hipMemsetAsync(pk.lk_or_d.p, 0, (size_t)NLT * LKF * sizeof(unsigned long long), st));
     // permute_expression_pair (lookup/prover.rs:410-494): sort by Ord (canonical value),
     // match, fill leftovers; then the bf + 1 random rows (input first, then table).
     // Every lookup's two columns go through ONE radix sort (radix.hip): column g = 2 j + side
@@ -713,7 +686,7 @@ int ProofRun::lookup_permuted() {
     // (single-owner stages, and only while every lookup sorts by its
     // window -- a full sort writes its table group).  Otherwise two groups per lookup.
     std::vector<int> tsrc(NLT), gi0(NLT, -1), gi1(NLT, -1);
-    bool share = !lk_wide && pk.lk_trep.size() == (size_t)pk.NL && (int)pk.lk_hb.size() >= NLT;
+    bool share = !lk_wide && pk.lk_trep.size() == (size_t)pk.cs.NL && (int)pk.lk_hb.size() >= NLT;
     for (int j = 0; j < NLT && share; j++)
       if (lq[j] >= 0 && pk.lk_hb[j] == 0) share = false;
     int ntab = 0;
@@ -721,7 +694,7 @@ int ProofRun::lookup_permuted() {
       tsrc[j] = j;
       if (lq[j] < 0) continue;
       if (share) {
-        const int r = (j / pk.NL) * pk.NL + pk.lk_trep[j % pk.NL];
+        const int r = (j / pk.cs.NL) * pk.cs.NL + pk.lk_trep[j % pk.cs.NL];
         if (lq[r] >= 0) tsrc[j] = r;
         gi0[j] = lq[j];
         if (tsrc[j] == j) gi1[j] = nown + ntab++;
@@ -734,29 +707,23 @@ int ProofRun::lookup_permuted() {
     const int G = share ? nown + ntab : 2 * nown;
     int gbits = 0;
     while ((1 << gbits) < G) gbits++;
-    if (NLT && (size_t)G * u > pk.lkb_len) {  // grow-only batch buffers
+    if (NLT) {  // the batch buffers, sized before anything below takes an address in them
       const size_t m = (size_t)G * u;
-      PALLOC(pk.pool, pk.lkb_canon, m);
+      HIPCHK(pk.lkb_canon.ensure(m));
       for (int q = 0; q < 2; q++) {
-        PALLOC(pk.pool, pk.lkb_key[q], m);
-        PALLOC(pk.pool, pk.lkb_idx[q], m);
+        HIPCHK(pk.lkb_key[q].ensure(m));
+        HIPCHK(pk.lkb_idx[q].ensure(m));
       }
-      const size_t sb = std::max(std::max(radix_sort_scratch_bytes(m), radix_sort_scratch_bytes(n)),
-                                 compact_scratch_bytes(n));
-      HIPCHK(pk.pool.get(&pk.lkb_scr, sb));
-      pk.lkb_len = m;
+      HIPCHK(pk.lkb_scr.ensure(std::max(std::max(radix_sort_scratch_bytes(m), radix_sort_scratch_bytes(n)),
+                                        compact_scratch_bytes(n))));
     }
     // the match and fill of lookup j from its sorted columns (pk.ck_a2 input, pk.ck_t2 table)
     // every lookup's counters and flags cleared at once (a redo clears its own again)
-    if ((size_t)NLT > pk.lk_cf_n || u > pk.lk_cf_u) {
-      PALLOC(pk.pool, pk.lk_counters, (size_t)NLT * LKC);
-      PALLOC(pk.pool, pk.lk_flags, (size_t)NLT * u);
-      pk.lk_cf_n = (size_t)NLT;
-      pk.lk_cf_u = u;
-    }
+    HIPCHK(pk.lk_counters.ensure((size_t)NLT * LKC));
+    HIPCHK(pk.lk_flags.ensure((size_t)NLT * u));
     if (NLT) {
-      HIPCHK(hipMemsetAsync(pk.lk_counters, 0, (size_t)NLT * LKC * sizeof(uint32_t), st));
-      HIPCHK(hipMemsetAsync(pk.lk_flags, 1, (size_t)NLT * u, st));
+      HIPCHK(hipMemsetAsync(pk.lk_counters.p, 0, (size_t)NLT * LKC * sizeof(uint32_t), st));
+      HIPCHK(hipMemsetAsync(pk.lk_flags.p, 1, (size_t)NLT * u, st));
     }
     // scratch set q (0: the key's own) for the gathers and matches
     struct LkSet {
@@ -766,14 +733,14 @@ int ProofRun::lookup_permuted() {
       void* scr;
     };
     auto lk_set = [&](int q) -> LkSet {
-      if (q == 0) return LkSet{pk.ck_a2, pk.ck_t2, pk.ck_left, pk.rep_flag, pk.rep_rows, pk.lkb_scr};
+      if (q == 0) return LkSet{pk.ck_a2, pk.ck_t2, pk.ck_left, pk.rep_flag, pk.rep_rows, pk.lkb_scr.p};
       return LkSet{pk.lks_a2[q], pk.lks_t2[q], pk.lks_left[q], pk.lks_rep[q], pk.lks_rows[q], pk.lks_scr[q]};
     };
     auto match_fill = [&](int j, bool again, const LkSet& z, hipStream_t sj) -> int {
-      const int ci = j / pk.NL, l = j % pk.NL;
+      const int ci = j / pk.cs.NL, l = j % pk.cs.NL;
       CircuitWs& w = *W[ci];
-      uint32_t* cnt = pk.lk_counters + (size_t)LKC * j;
-      uint8_t* flags = pk.lk_flags + (size_t)j * u;
+      uint32_t* cnt = pk.lk_counters.p + (size_t)LKC * j;
+      uint8_t* flags = pk.lk_flags.p + (size_t)j * u;
       if (again) {
         HIPCHK(hipMemsetAsync(flags, 1, u, sj));
         HIPCHK(hipMemsetAsync(cnt, 0, LKC * sizeof(uint32_t), sj));
@@ -784,30 +751,30 @@ int ProofRun::lookup_permuted() {
       HIPCHK(lookup_assign(z.a2, z.rep, u, w.lk_ap[l], w.lk_sp[l], sj));
       HIPCHK(lookup_scatter(z.left, z.rows, cnt + 1, u, w.lk_sp[l], sj));
       if (again)
-        HIPCHK(hipMemcpyAsync(pk.lk_cnt + (size_t)LKC * j, cnt, LKC * sizeof(uint32_t), hipMemcpyDeviceToHost, sj));
+        HIPCHK(hipMemcpyAsync(pk.lk_cnt.p + (size_t)LKC * j, cnt, LKC * sizeof(uint32_t), hipMemcpyDeviceToHost, sj));
       return H2G_OK;  // the blinding rows of every lookup land together below (upload_rows_batch)
     };
     // the full sort of lookup j's columns into pk.ck_a2 / ck_t2 (radix sorts on the limbs,
     // in lookup j's own regions of the batch's key / index buffers)
     auto full_sort = [&](int j) -> int {
-      const int ci = j / pk.NL, l = j % pk.NL;
+      const int ci = j / pk.cs.NL, l = j % pk.cs.NL;
       CircuitWs& w = *W[ci];
       const Fr* srcs[2] = {w.lk_a[l], w.lk_s[l]};
       CanonKey* sorted[2] = {pk.ck_a2, pk.ck_t2};
       for (int side = 0; side < 2; side++) {
-        CanonKey* canon = pk.lkb_canon + (size_t)(side ? gi1[j] : gi0[j]) * u;
-        HIPCHK(lookup_keys(srcs[side], u, 0, canon, nullptr, nullptr, pk.lk_or_d + (size_t)LKF * j, st));
+        CanonKey* canon = pk.lkb_canon.p + (size_t)(side ? gi1[j] : gi0[j]) * u;
+        HIPCHK(lookup_keys(srcs[side], u, 0, canon, nullptr, nullptr, pk.lk_or_d.p + (size_t)LKF * j, st));
         const size_t o = (size_t)gi0[j] * u;  // (the sort's scratch: the lookup's input group)
-        uint64_t *k0 = pk.lkb_key[0] + o, *k1 = pk.lkb_key[1] + o;
-        uint32_t *i0 = pk.lkb_idx[0] + o, *i1 = pk.lkb_idx[1] + o;
+        uint64_t *k0 = pk.lkb_key[0].p + o, *k1 = pk.lkb_key[1].p + o;
+        uint32_t *i0 = pk.lkb_idx[0].p + o, *i1 = pk.lkb_idx[1].p + o;
         HIPCHK(iota_u32(i0, u, st));
         for (int limb = 0; limb < 4; limb++) {  // least significant first; 8 passes end where they began
           HIPCHK(canon_limb_keys(canon, i0, u, limb, k0, st));
           bool alt = false;
-          HIPCHK(radix_sort_pairs(k0, i0, k1, i1, u, 0, 64, pk.lkb_scr, st, &alt));
+          HIPCHK(radix_sort_pairs(k0, i0, k1, i1, u, 0, 64, pk.lkb_scr.p, st, &alt));
           if (alt) return fail(H2G_ERR_STATE, "lookup full sort: unexpected pass parity");
         }
-        HIPCHK(lookup_gather(canon, i0, u, sorted[side], pk.lk_or_d + (size_t)LKF * j + 4, st));
+        HIPCHK(lookup_gather(canon, i0, u, sorted[side], pk.lk_or_d.p + (size_t)LKF * j + 4, st));
       }
       return H2G_OK;
     };
@@ -831,8 +798,8 @@ int ProofRun::lookup_permuted() {
         return H2G_OK;
       };
       for (int ci = 0; ci < ncirc; ci++)
-        for (int l = 0; l < pk.NL; l++)
-          if (lq[ci * pk.NL + l] >= 0) {
+        for (int l = 0; l < pk.cs.NL; l++)
+          if (lq[ci * pk.cs.NL + l] >= 0) {
             RCCHK(add(pk.seg_lk_in[l], *W[ci], W[ci]->lk_a[l]));
             RCCHK(add(pk.seg_lk_tab[l], *W[ci], W[ci]->lk_s[l]));
           }
@@ -840,14 +807,14 @@ int ProofRun::lookup_permuted() {
     }
     LookupKeysBatch kb;  // every column's keys, batched launches
     kb.n = u;
-    kb.canon = pk.lkb_canon;
-    kb.key = pk.lkb_key[0];
-    kb.idx = pk.lkb_idx[0];
+    kb.canon = pk.lkb_canon.p;
+    kb.key = pk.lkb_key[0].p;
+    kb.idx = pk.lkb_idx[0].p;
     kb.kbits = 48;
     kb.kmask = (1ull << 48) - 1;
     for (int ci = 0; ci < ncirc; ci++)
-      for (int l = 0; l < pk.NL; l++) {
-        const int j = ci * pk.NL + l;
+      for (int l = 0; l < pk.cs.NL; l++) {
+        const int j = ci * pk.cs.NL + l;
         for (int which = 0; which < 2; which++) {
           Fr* r = rows.data() + ((size_t)2 * j + which) * (bf + 1);
           for (int i = 0; i <= bf; i++) r[i] = rng.random_fr();
@@ -867,22 +834,22 @@ int ProofRun::lookup_permuted() {
           kb.in[kb.count] = srcs[side];
           kb.s[kb.count] = shift;
           kb.g[kb.count] = side ? gi1[j] : gi0[j];
-          kb.d_or[kb.count++] = pk.lk_or_d + (size_t)LKF * j;
+          kb.d_or[kb.count++] = pk.lk_or_d.p + (size_t)LKF * j;
         }
       }
     HIPCHK(lookup_keys_batch(kb, st));
     if (nown) {
       bool alt = false;
-      HIPCHK(radix_sort_pairs(pk.lkb_key[0], pk.lkb_idx[0], pk.lkb_key[1], pk.lkb_idx[1], (size_t)G * u, 0,
-                              48 + gbits, pk.lkb_scr, st, &alt));
-      const uint32_t* sidx = pk.lkb_idx[alt ? 1 : 0];
+      HIPCHK(radix_sort_pairs(pk.lkb_key[0].p, pk.lkb_idx[0].p, pk.lkb_key[1].p, pk.lkb_idx[1].p, (size_t)G * u, 0,
+                              48 + gbits, pk.lkb_scr.p, st, &alt));
+      const uint32_t* sidx = pk.lkb_idx[alt ? 1 : 0].p;
       // the lookups' gathers and matches on LKS streams when none needs the full sort (its
       // radix passes use the key's scratch); lookup q-th of this rank on stream q mod LKS
       bool multi = nown > 1;
       for (int j = 0; j < NLT; j++) multi = multi && (lq[j] < 0 || used[j] != 0);
       const int S = multi ? std::min(nown, ProvingKey::LKS) : 1;
       if (S > 1) {
-        if (pk.lks_n < u) {
+        if (!pk.lks_a2[1]) {  // (u is the key's: these never grow)
           for (int q = 1; q < ProvingKey::LKS; q++) {
             PALLOC(pk.pool, pk.lks_a2[q], u);
             PALLOC(pk.pool, pk.lks_t2[q], u);
@@ -891,12 +858,9 @@ int ProofRun::lookup_permuted() {
             PALLOC(pk.pool, pk.lks_rows[q], u);
             HIPCHK(pk.pool.get(&pk.lks_scr[q], compact_scratch_bytes(u)));
           }
-          pk.lks_n = u;
         }
-        if (!pk.lk_st[0]) {
-          for (int q = 0; q < ProvingKey::LKS; q++) HIPCHK(hipStreamCreateWithFlags(&pk.lk_st[q], hipStreamNonBlocking));
-          for (int q = 0; q <= ProvingKey::LKS; q++) HIPCHK(hipEventCreateWithFlags(&pk.lk_ev[q], hipEventDisableTiming));
-        }
+        for (Stream& s : pk.lk_st) HIPCHK(s.ensure());
+        for (Event& e : pk.lk_ev) HIPCHK(e.ensure());
         HIPCHK(hipEventRecord(pk.lk_ev[0], st));  // the sort is done
         for (int q = 0; q < S; q++) HIPCHK(hipStreamWaitEvent(pk.lk_st[q], pk.lk_ev[0], 0));
       }
@@ -912,8 +876,8 @@ int ProofRun::lookup_permuted() {
         } else {
           for (int side = 0; side < 2; side++) {
             const size_t g = (size_t)(side ? gi1[j] : gi0[j]);
-            HIPCHK(lookup_gather(pk.lkb_canon + g * u, sidx + g * u, u, side ? z.t2 : z.a2,
-                                 pk.lk_or_d + (size_t)LKF * j + 4, sj));
+            HIPCHK(lookup_gather(pk.lkb_canon.p + g * u, sidx + g * u, u, side ? z.t2 : z.a2,
+                                 pk.lk_or_d.p + (size_t)LKF * j + 4, sj));
           }
         }
         RCCHK(match_fill(j, false, z, sj));
@@ -926,9 +890,9 @@ int ProofRun::lookup_permuted() {
       }
     }
     if (NLT) {
-      HIPCHK(hipMemcpyAsync(pk.lk_cnt, pk.lk_counters, (size_t)NLT * LKC * sizeof(uint32_t), hipMemcpyDeviceToHost,
+      HIPCHK(hipMemcpyAsync(pk.lk_cnt.p, pk.lk_counters.p, (size_t)NLT * LKC * sizeof(uint32_t), hipMemcpyDeviceToHost,
                             st));
-      HIPCHK(hipMemcpyAsync(pk.lk_or_h, pk.lk_or_d, (size_t)NLT * LKF * sizeof(unsigned long long),
+      HIPCHK(hipMemcpyAsync(pk.lk_or_h.p, pk.lk_or_d.p, (size_t)NLT * LKF * sizeof(unsigned long long),
                             hipMemcpyDeviceToHost, st));
       HIPCHK(hipStreamSynchronize(st));  // counters and value masks landed; rows (host) read
     }
@@ -939,7 +903,7 @@ int ProofRun::lookup_permuted() {
     std::vector<char> redone(NLT, 0);  // a lookup matched against a shared table redone with it
     for (int j = 0; j < NLT; j++) {
       if (lq[j] < 0 || used[j] == 0) continue;
-      const unsigned long long* f = pk.lk_or_h + (size_t)LKF * j;
+      const unsigned long long* f = pk.lk_or_h.p + (size_t)LKF * j;
       int hb = 0;
       for (int q = 3; q >= 0 && !hb; q--)
         if (f[q]) hb = 64 * q + 64 - __builtin_clzll(f[q]);
@@ -955,21 +919,21 @@ int ProofRun::lookup_permuted() {
     }
     if (redo) HIPCHK(hipStreamSynchronize(st));
     {  // the blinding rows of A'_l and S'_l of every lookup this rank sorted, one upload
-      RCCHK(blind_stage(pk, rows.size()));
+      HIPCHK(pk.blind_d.ensure(rows.size()));
       std::vector<CopySeg> segs;
       for (int j = 0; j < NLT; j++) {
         if (lq[j] < 0) continue;
-        CircuitWs& w = *W[j / pk.NL];
-        const int l = j % pk.NL;
+        CircuitWs& w = *W[j / pk.cs.NL];
+        const int l = j % pk.cs.NL;
         for (int which = 0; which < 2; which++)
-          segs.push_back(CopySeg{pk.blind_d + ((size_t)2 * j + which) * (bf + 1), (which ? w.lk_sp[l] : w.lk_ap[l]) + u,
+          segs.push_back(CopySeg{pk.blind_d.p + ((size_t)2 * j + which) * (bf + 1), (which ? w.lk_sp[l] : w.lk_ap[l]) + u,
                                  (uint64_t)(bf + 1)});
       }
       RCCHK(upload_rows_batch(pk, rows.data(), rows.size(), segs, st));
     }
     bool lk_ok = true;
     for (int j = 0; j < NLT; j++) {
-      const uint32_t* cnt = pk.lk_cnt + (size_t)LKC * j;
+      const uint32_t* cnt = pk.lk_cnt.p + (size_t)LKC * j;
       if (lq[j] >= 0 && (cnt[2] != 0 || cnt[0] != cnt[1])) lk_ok = false;
     }
     if (lk_wide) {  // every rank learns whether any owner's lookup failed (none may hang in a collective)
@@ -981,7 +945,7 @@ int ProofRun::lookup_permuted() {
     std::vector<const Fr*> perm_cols;  // (A'_l, S'_l) in transcript order
     std::vector<Fr*> perm_polys, perm_cosets;
     for (int ci = 0; ci < ncirc; ci++)
-      for (int l = 0; l < pk.NL; l++) {
+      for (int l = 0; l < pk.cs.NL; l++) {
         CircuitWs& w = *W[ci];
         perm_cols.push_back(w.lk_ap[l]);
         perm_cols.push_back(w.lk_sp[l]);
@@ -1000,11 +964,7 @@ int ProofRun::lookup_permuted() {
     // where a column belongs to its owner)
     size_t owned = 0;
     for (int i = 0; i < 2 * NLT; i++) owned += own2[i] == g_spmd.rank;
-    const size_t need = std::max<size_t>(owned, 1) * n;
-    if (need > pk.lk_diff_len) {
-      PALLOC(pk.pool, pk.lk_diff, need);
-      pk.lk_diff_len = need;
-    }
+    HIPCHK(pk.lk_diff.ensure(std::max<size_t>(owned, 1) * n));
     PrefixDiff pd{};
     int m = 0;
     size_t slot = 0;
@@ -1013,7 +973,7 @@ int ProofRun::lookup_permuted() {
         com_cols[i] = perm_cols[i];
         continue;
       }
-      Fr* e = pk.lk_diff + (slot++) * n;
+      Fr* e = pk.lk_diff.p + (slot++) * n;
       com_cols[i] = e;
       pd.a[m] = perm_cols[i];
       pd.e[m] = e;
@@ -1039,7 +999,7 @@ int ProofRun::lookup_permuted() {
     }
     RCCHK(rng_ok());
   }
-  if (pk.NL) clk.mark("lookup permuted");
+  if (pk.cs.NL) clk.mark("lookup permuted");
   return H2G_OK;
 }
 
@@ -1052,7 +1012,7 @@ int ProofRun::permutation_products() {
   // large MSMs start as soon as their set's z is ready; small ones wait and go as a batch
   const bool perm_batched = commit_batch_chunk(prm, n, SRS_LAGRANGE) > 1;
   for (CircuitWs* w : W)
-    for (int s = 0; s < pk.nsets; s++) {
+    for (int s = 0; s < pk.cs.nsets; s++) {
       all_z_lag.push_back(w->z_lag[s]);
       all_z.push_back(w->z[s]);
       all_z_coset.push_back(w->z_coset[s]);
@@ -1072,8 +1032,8 @@ int ProofRun::permutation_products() {
       zs[i] = all_z[i] + plo;
     }
     for (int ci = 0; ci < ncirc; ci++)
-      for (int s = 0; s < pk.nsets; s++) {
-        const int c0 = s * pk.chunk_len, c1 = std::min(c0 + pk.chunk_len, pk.P);
+      for (int s = 0; s < pk.cs.nsets; s++) {
+        const int c0 = s * pk.cs.chunk_len, c1 = std::min(c0 + pk.cs.chunk_len, pk.cs.P);
         for (int c = c0; c < c1 && len; c += PERM_MAXC) {
           PermCols pc;
           pc.m = std::min(PERM_MAXC, c1 - c);
@@ -1081,14 +1041,14 @@ int ProofRun::permutation_products() {
             pc.v[j] = col_vals(*W[ci], c + j) + plo;
             pc.sigma[j] = pk.sigma_lag[c + j] + plo;
           }
-          HIPCHK(perm_denominators(zl[(size_t)ci * pk.nsets + s], len, pc, beta, gamma, c == c0, st));
+          HIPCHK(perm_denominators(zl[(size_t)ci * pk.cs.nsets + s], len, pc, beta, gamma, c == c0, st));
         }
       }
     if (len) HIPCHK(poly_batch_invert_multi(zl.data(), zs.data(), NST, len, st));
     for (int ci = 0; ci < ncirc; ci++) {
       Fr deltaomega = Fr::one();
-      for (int s = 0; s < pk.nsets; s++) {
-        const int c0 = s * pk.chunk_len, c1 = std::min(c0 + pk.chunk_len, pk.P);
+      for (int s = 0; s < pk.cs.nsets; s++) {
+        const int c0 = s * pk.cs.chunk_len, c1 = std::min(c0 + pk.cs.chunk_len, pk.cs.P);
         for (int c = c0; c < c1; c += PERM_MAXC) {
           PermCols pc;
           pc.m = std::min(PERM_MAXC, c1 - c);
@@ -1097,7 +1057,7 @@ int ProofRun::permutation_products() {
             pc.beta_delta[j] = deltaomega * beta;
             deltaomega = deltaomega * fr_delta();
           }
-          if (len) HIPCHK(perm_numerators(zl[(size_t)ci * pk.nsets + s], len, pc, gamma, pk.om, st, plo));
+          if (len) HIPCHK(perm_numerators(zl[(size_t)ci * pk.cs.nsets + s], len, pc, gamma, pk.om, st, plo));
         }
       }
     }
@@ -1115,8 +1075,8 @@ int ProofRun::permutation_products() {
     std::vector<Fr> lzp(NST);  // z at this slab's first row = z_0 * (the slabs below)
     for (int ci = 0; ci < ncirc; ci++) {
       Fr lz = Fr::one();
-      for (int s = 0; s < pk.nsets; s++) {
-        const int i = ci * pk.nsets + s;
+      for (int s = 0; s < pk.cs.nsets; s++) {
+        const int i = ci * pk.cs.nsets + s;
         Fr below = Fr::one(), all = Fr::one();
         for (int r = 0; r < Wsp; r++) {
           if (r < me) below = below * allp[(size_t)r * NST + i];
@@ -1126,17 +1086,14 @@ int ProofRun::permutation_products() {
         lz = lz * all;
       }
     }
-    if (!pk.perm_lz || pk.perm_lz_len < (size_t)NST) {
-      PALLOC(pk.pool, pk.perm_lz, NST);
-      pk.perm_lz_len = (size_t)NST;
-    }
-    HIPCHK(pk_upload(pk, pk.perm_lz, lzp.data(), NST * sizeof(Fr), st));
+    HIPCHK(pk.perm_lz.ensure(std::max(NST, 1)));
+    HIPCHK(pk_upload(pk, pk.perm_lz.p, lzp.data(), NST * sizeof(Fr), st));
     for (int i = 0; i < NST; i++) {
       Fr* blind_rows = perm_blind.data() + (size_t)i * bf;
       for (int q = 0; q < bf; q++) blind_rows[q] = rng.random_fr();
       (void)rng.random_fr();  // blind
       HIPCHK(pk_upload(pk, pk.small, blind_rows, bf * sizeof(Fr), st));
-      HIPCHK(perm_z_assemble(all_z_lag[i], n, bf, all_z[i], pk.perm_lz + i, pk.small, st, plo, phi));
+      HIPCHK(perm_z_assemble(all_z_lag[i], n, bf, all_z[i], pk.perm_lz.p + i, pk.small, st, plo, phi));
     }
     HIPCHK(hipStreamSynchronize(st));  // lzp (host) was read
     RCCHK(commit_launch_batch(d, prm, (const Fr* const*)all_z_lag.data(), NST, n, SRS_LAGRANGE, st, perm_tk.data()));
@@ -1152,8 +1109,8 @@ int ProofRun::permutation_products() {
     // every set's denominators (into z_lag), one batched inversion over all circuits'
     // sets (z as its scratch until the iNTT fills it), then per set numerators, scan and z
     for (int ci = 0; ci < ncirc; ci++)
-      for (int s = 0; s < pk.nsets; s++) {
-        const int c0 = s * pk.chunk_len, c1 = std::min(c0 + pk.chunk_len, pk.P);
+      for (int s = 0; s < pk.cs.nsets; s++) {
+        const int c0 = s * pk.cs.chunk_len, c1 = std::min(c0 + pk.cs.chunk_len, pk.cs.P);
         for (int c = c0; c < c1; c += PERM_MAXC) {
           PermCols pc;
           pc.m = std::min(PERM_MAXC, c1 - c);
@@ -1172,9 +1129,9 @@ int ProofRun::permutation_products() {
       CircuitWs& w = *W[ci];
       HIPCHK(hipMemcpyAsync(pk.last_z, pk.one, sizeof(Fr), hipMemcpyDeviceToDevice, st));  // z_0 starts at one
       Fr deltaomega = Fr::one();
-      for (int s = 0; s < pk.nsets; s++) {
-        Fr* blind_rows = perm_blind.data() + ((size_t)ci * pk.nsets + s) * bf;
-        const int c0 = s * pk.chunk_len, c1 = std::min(c0 + pk.chunk_len, pk.P);
+      for (int s = 0; s < pk.cs.nsets; s++) {
+        Fr* blind_rows = perm_blind.data() + ((size_t)ci * pk.cs.nsets + s) * bf;
+        const int c0 = s * pk.cs.chunk_len, c1 = std::min(c0 + pk.cs.chunk_len, pk.cs.P);
         Fr* prod = w.z_lag[s];
         for (int c = c0; c < c1; c += PERM_MAXC) {
           PermCols pc;
@@ -1202,7 +1159,7 @@ int ProofRun::permutation_products() {
           dump("v0", col_vals(w, 0), n, st);
         }
         if (!perm_batched)
-          RCCHK(commit_launch(d, prm, w.z_lag[s], n, SRS_LAGRANGE, st, &perm_tk[(size_t)ci * pk.nsets + s]));
+          RCCHK(commit_launch(d, prm, w.z_lag[s], n, SRS_LAGRANGE, st, &perm_tk[(size_t)ci * pk.cs.nsets + s]));
       }
     }
     RCCHK(xform(std::vector<const Fr*>(all_z_lag.begin(), all_z_lag.end()), all_z, all_z_coset, nullptr));
@@ -1233,13 +1190,13 @@ int ProofRun::lookup_shuffle_products() {
       (void)rng.random_fr();  // product blind
     }
     if (nprod) {
-      RCCHK(blind_stage(pk, nprod * (size_t)bf));
-      HIPCHK(pk_upload(pk, pk.blind_d, prod_blind.data(), nprod * (size_t)bf * sizeof(Fr), st));
+      HIPCHK(pk.blind_d.ensure(nprod * (size_t)bf));
+      HIPCHK(pk_upload(pk, pk.blind_d.p, prod_blind.data(), nprod * (size_t)bf * sizeof(Fr), st));
     }
     // prod: the running product's factors, or (scanned) already its prefix products
     auto finish_z = [&](const Fr* prod, Fr* z_lag, Fr* z_poly, Fr* z_coset, bool scanned, bool here,
                         bool listed) -> int {
-      const Fr* rows_d = pk.blind_d + (zrow++) * (size_t)bf;
+      const Fr* rows_d = pk.blind_d.p + (zrow++) * (size_t)bf;
       if (!here) return H2G_OK;
       const Fr* pre = prod;
       if (!scanned) {
@@ -1259,7 +1216,7 @@ int ProofRun::lookup_shuffle_products() {
     // z_lag serves as the inversion's scratch until z is assembled into it
     std::vector<Fr*> dens, dens_scr;
     for (int ci = 0, j = 0; ci < ncirc; ci++)
-      for (int l = 0; l < pk.NL; l++, j++) {
+      for (int l = 0; l < pk.cs.NL; l++, j++) {
         if (!mine(j)) continue;
         CircuitWs* w = W[ci];
         HIPCHK(lookup_prod_den(w->lk_ap[l], w->lk_sp[l], beta, gamma, w->lk_z_poly[l], n, st));
@@ -1269,7 +1226,7 @@ int ProofRun::lookup_shuffle_products() {
     if (!dens.empty()) HIPCHK(poly_batch_invert_multi(dens.data(), dens_scr.data(), (int)dens.size(), n, st));
     // numerators, then every lookup's running product in one batched scan (in place)
     for (int ci = 0, j = 0; ci < ncirc; ci++)
-      for (int l = 0; l < pk.NL; l++, j++)
+      for (int l = 0; l < pk.cs.NL; l++, j++)
         if (mine(j)) HIPCHK(lookup_prod_num(W[ci]->lk_a[l], W[ci]->lk_s[l], beta, gamma, W[ci]->lk_z_poly[l], n, st));
     if (!dens.empty())
       HIPCHK(poly_prefix_product_multi((const Fr* const*)dens.data(), dens.data(), (int)dens.size(), n, pk.scr,
@@ -1277,7 +1234,7 @@ int ProofRun::lookup_shuffle_products() {
     std::vector<const Fr*> lkz_lag;
     std::vector<Fr*> lkz_poly, lkz_cst;
     for (int ci = 0, j = 0; ci < ncirc; ci++)
-      for (int l = 0; l < pk.NL; l++, j++) {
+      for (int l = 0; l < pk.cs.NL; l++, j++) {
         CircuitWs* w = W[ci];
         RCCHK(finish_z(w->lk_z_poly[l], w->lk_z[l], w->lk_z_poly[l], w->lk_zc[l], true, mine(j), !lz_wide));
         lkz_lag.push_back(w->lk_z[l]);
@@ -1285,7 +1242,7 @@ int ProofRun::lookup_shuffle_products() {
         lkz_cst.push_back(w->lk_zc[l]);
       }
     for (CircuitWs* w : W)
-      for (int s = 0; s < pk.NS; s++) {
+      for (int s = 0; s < pk.cs.NS; s++) {
         RCCHK(compress(*w, pk.seg_sh_in[s], pk.tmp_a));
         RCCHK(compress(*w, pk.seg_sh_sh[s], pk.tmp_b));
         HIPCHK(shuffle_prod_den(pk.tmp_b, gamma, pk.mod, n, st));
@@ -1309,7 +1266,7 @@ int ProofRun::lookup_shuffle_products() {
     for (int j = 0; j < NLT; j++) lkz_tk[j] = zt[j];
     for (int j = 0; j < NSH; j++) shz_tk[j] = zt[NLT + j];
   }
-  if (pk.NL + pk.NS) clk.mark("lookup/shuffle products");
+  if (pk.cs.NL + pk.cs.NS) clk.mark("lookup/shuffle products");
   return H2G_OK;
 }
 
@@ -1331,10 +1288,10 @@ int ProofRun::vanishing_commit() {
     }
     if (!van_early) {
       van_seeds = drawn;
-      HIPCHK(pk_upload(pk, pk.d_seeds, van_seeds.data(), van_seeds.size() * 4, st));
-      HIPCHK(pk_upload(pk, pk.d_offsets, van_off.data(), van_off.size() * 8, st));
+      HIPCHK(pk_upload(pk, pk.d_seeds.p, van_seeds.data(), van_seeds.size() * 4, st));
+      HIPCHK(pk_upload(pk, pk.d_offsets.p, van_off.data(), van_off.size() * 8, st));
       // a slab-mode rank draws only its coefficients (and the halo) of the random polynomial
-      HIPCHK(chacha_random_poly(pk.random_poly, n, pk.d_seeds, pk.d_offsets, (int)van_off.size(), st, sl.lo,
+      HIPCHK(chacha_random_poly(pk.random_poly, n, pk.d_seeds.p, pk.d_offsets.p, (int)van_off.size(), st, sl.lo,
                                 sl.hi1));
     }
     (void)rng.random_fr();  // random_blind
@@ -1344,7 +1301,7 @@ int ProofRun::vanishing_commit() {
   // the instance columns' cosets do not depend on y: they overlap the permutation /
   // vanishing MSMs (the advice went to coefficients and cosets under its own MSMs)
   for (CircuitWs* w : W)
-    RCCHK(ext_cosets(d, pk, (const Fr* const*)w->inst_poly.data(), w->inst_coset.data(), pk.I, st));
+    RCCHK(ext_cosets(d, pk, (const Fr* const*)w->inst_poly.data(), w->inst_coset.data(), pk.cs.I, st));
   {
     std::vector<MsmTicket*> tl;
     for (auto* tks : {&perm_tk, &lkz_tk, &shz_tk})
@@ -1380,7 +1337,7 @@ int ProofRun::eval_h() {
     a.ext_omega = pk.eo;
     a.ext = ext;
     a.rot_scale = pk.rot_scale;
-    a.t_evals = D.d_t;
+    a.t_evals = D.d_t.p;
     a.t_mask = D.t_evals.size() - 1;
     a.acc_in = ci > 0 ? pk.h_ext : nullptr;
     a.out = pk.h_ext;
@@ -1408,7 +1365,7 @@ int ProofRun::eval_h() {
         a.ext_omega = pk.om;
         a.ext = n;
         a.rot_scale = 1;
-        a.t_evals = D.d_t + t;  // t(X) is constant on a sub-coset
+        a.t_evals = D.d_t.p + t;  // t(X) is constant on a sub-coset
         a.t_mask = 0;
         a.acc_in = ci > 0 ? slot : nullptr;
         a.out = slot;
@@ -1441,7 +1398,7 @@ int ProofRun::eval_h() {
 // that received h by slabs holds its slab of each piece already)
 int ProofRun::h_commit() {
   if (!h_slabs) RCCHK(extended_to_coeff(d, D, pk.h_ext, pk.h_coeff, st));
-  const int npieces = pk.degree - 1;
+  const int npieces = pk.cs.degree - 1;
   for (int p = 0; p < npieces; p++) (void)rng.random_fr();  // h blinds
   RCCHK(rng_ok());
   {
@@ -1481,29 +1438,29 @@ int ProofRun::h_commit() {
 // ---- the polynomial openings (prover.rs:840-889) and their evaluations
 int ProofRun::openings_and_evals() {
   for (const CircuitWs* w : W) {
-    for (int c = 0; c < pk.A; c++) polys.push_back({w->adv_poly[c], n});
-    for (int s = 0; s < pk.nsets; s++) polys.push_back({w->z[s], n});
-    for (int l = 0; l < pk.NL; l++) {
+    for (int c = 0; c < pk.cs.A; c++) polys.push_back({w->adv_poly[c], n});
+    for (int s = 0; s < pk.cs.nsets; s++) polys.push_back({w->z[s], n});
+    for (int l = 0; l < pk.cs.NL; l++) {
       polys.push_back({w->lk_z_poly[l], n});
       polys.push_back({w->lk_ap_poly[l], n});
       polys.push_back({w->lk_sp_poly[l], n});
     }
-    for (int s = 0; s < pk.NS; s++) polys.push_back({w->sh_z_poly[s], n});
+    for (int s = 0; s < pk.cs.NS; s++) polys.push_back({w->sh_z_poly[s], n});
   }
   const int id_fix = (int)polys.size();
   if (coef_send || coef_recv) {  // the per-circuit coefficient columns' slabs, owners -> the others
     std::vector<Fr*> cols;     // (the columns of wide stages reached every rank from their owners)
     for (int ci = 0; ci < ncirc; ci++)
       for (int i = 0; i < per_c; i++) {
-        if (i < pk.A && adv_shard[(size_t)ci * pk.A + i]) continue;
-        if (lk_shard && i >= pk.A + pk.nsets && i < pk.A + pk.nsets + 3 * pk.NL) continue;
+        if (i < pk.cs.A && adv_shard[(size_t)ci * pk.cs.A + i]) continue;
+        if (lk_shard && i >= pk.cs.A + pk.cs.nsets && i < pk.cs.A + pk.cs.nsets + 3 * pk.cs.NL) continue;
         cols.push_back(const_cast<Fr*>(polys[(size_t)ci * per_c + i].p));
       }
     RCCHK(coef_exchange(pk, cols, st));
   }
-  for (int c = 0; c < pk.F; c++) polys.push_back({pk.fixed_poly[c], n});
+  for (int c = 0; c < pk.cs.F; c++) polys.push_back({pk.fixed_poly[c], n});
   const int id_sig = (int)polys.size();
-  for (int c = 0; c < pk.P; c++) polys.push_back({pk.sigma_poly[c], n});
+  for (int c = 0; c < pk.cs.P; c++) polys.push_back({pk.sigma_poly[c], n});
   const int id_h = (int)polys.size();
   polys.push_back({pk.h_poly, n});
   const int id_r = (int)polys.size();
@@ -1511,13 +1468,13 @@ int ProofRun::openings_and_evals() {
   const Fr x_next = rotate_omega(D, x, 1), x_last = rotate_omega(D, x, -(bf + 1));
   const Fr x_prev = rotate_omega(D, x, -1);
   for (int ci = 0; ci < ncirc; ci++) {  // per circuit: advice, permutation, lookups, shuffles
-    for (auto& q : pk.adv_q) queries.push_back({id_adv(ci) + q.index, rotate_omega(D, x, q.rot)});
-    for (int s = 0; s < pk.nsets; s++) {  // permutation/prover.rs:300-333
+    for (auto& q : pk.cs.adv_q) queries.push_back({id_adv(ci) + q.index, rotate_omega(D, x, q.rot)});
+    for (int s = 0; s < pk.cs.nsets; s++) {  // permutation/prover.rs:300-333
       queries.push_back({id_z(ci) + s, x});
       queries.push_back({id_z(ci) + s, x_next});
     }
-    for (int s = pk.nsets - 2; s >= 0; s--) queries.push_back({id_z(ci) + s, x_last});
-    for (int l = 0; l < pk.NL; l++) {  // lookup/prover.rs:364-405
+    for (int s = pk.cs.nsets - 2; s >= 0; s--) queries.push_back({id_z(ci) + s, x_last});
+    for (int l = 0; l < pk.cs.NL; l++) {  // lookup/prover.rs:364-405
       const int zi = id_lk(ci) + 3 * l;
       queries.push_back({zi, x});
       queries.push_back({zi + 1, x});
@@ -1525,13 +1482,13 @@ int ProofRun::openings_and_evals() {
       queries.push_back({zi + 1, x_prev});
       queries.push_back({zi, x_next});
     }
-    for (int s = 0; s < pk.NS; s++) {  // shuffle/prover.rs:234-254
+    for (int s = 0; s < pk.cs.NS; s++) {  // shuffle/prover.rs:234-254
       queries.push_back({id_sh(ci) + s, x});
       queries.push_back({id_sh(ci) + s, x_next});
     }
   }
-  for (auto& q : pk.fix_q) queries.push_back({id_fix + q.index, rotate_omega(D, x, q.rot)});
-  for (int c = 0; c < pk.P; c++) queries.push_back({id_sig + c, x});
+  for (auto& q : pk.cs.fix_q) queries.push_back({id_fix + q.index, rotate_omega(D, x, q.rot)});
+  for (int c = 0; c < pk.cs.P; c++) queries.push_back({id_sig + c, x});
   queries.push_back({id_h, x});
   queries.push_back({id_r, x});
   ev_of.resize(polys.size());
@@ -1539,25 +1496,18 @@ int ProofRun::openings_and_evals() {
   evals.resize(ev_keys.size());
   {
     const int nreq = (int)ev_keys.size();
-    if (nreq > pk.max_reqs) {
-      PALLOC(pk.pool, pk.d_reqs, nreq);
-      PALLOC(pk.pool, pk.evals, nreq);
-      pk.max_reqs = nreq;
-    }
-    const size_t need = poly_eval_scratch_len(nreq, n);
-    if (need > pk.eval_scr_len) {
-      PALLOC(pk.pool, pk.eval_scr, need);
-      pk.eval_scr_len = need;
-    }
+    HIPCHK(pk.d_reqs.ensure(nreq));
+    HIPCHK(pk.evals.ensure(nreq));
+    HIPCHK(pk.eval_scr.ensure(poly_eval_scratch_len(nreq, n)));
     std::vector<EvalReq> reqs(nreq);
     for (int i = 0; i < nreq; i++) {  // a slab rank evaluates its coefficients [lo, hi) only
       const PolyRef& pr = polys[ev_keys[i].poly];
       const uint64_t len = pr.len > sl.lo ? std::min<uint64_t>(pr.len, sl.hi) - sl.lo : 0;
       reqs[i] = EvalReq{pr.p + (len ? sl.lo : 0), len, ev_keys[i].pt};
     }
-    HIPCHK(pk_upload(pk, pk.d_reqs, reqs.data(), nreq * sizeof(EvalReq), st));
-    HIPCHK(poly_eval_batch(pk.d_reqs, nreq, sl.hi - sl.lo, pk.evals, pk.eval_scr, st));
-    HIPCHK(hipMemcpyAsync(evals.data(), pk.evals, nreq * sizeof(Fr), hipMemcpyDeviceToHost, st));
+    HIPCHK(pk_upload(pk, pk.d_reqs.p, reqs.data(), nreq * sizeof(EvalReq), st));
+    HIPCHK(poly_eval_batch(pk.d_reqs.p, nreq, sl.hi - sl.lo, pk.evals.p, pk.eval_scr.p, st));
+    HIPCHK(hipMemcpyAsync(evals.data(), pk.evals.p, nreq * sizeof(Fr), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (slabs) {  // p(x) = sum_r x^lo_r (slab r's partial evaluation), summed in rank order
       std::vector<std::pair<Fr, Fr>> shift;  // (point, point^lo): a few distinct points
@@ -1578,18 +1528,18 @@ int ProofRun::openings_and_evals() {
     }
   }
   for (int ci = 0; ci < ncirc; ci++)  // [TRANSCRIPT-17] every circuit's advice evaluations
-    for (auto& q : pk.adv_q) tr.write_scalar(ev(id_adv(ci) + q.index, rotate_omega(D, x, q.rot)));
-  for (auto& q : pk.fix_q) tr.write_scalar(ev(id_fix + q.index, rotate_omega(D, x, q.rot)));
+    for (auto& q : pk.cs.adv_q) tr.write_scalar(ev(id_adv(ci) + q.index, rotate_omega(D, x, q.rot)));
+  for (auto& q : pk.cs.fix_q) tr.write_scalar(ev(id_fix + q.index, rotate_omega(D, x, q.rot)));
   tr.write_scalar(ev(id_r, x));
-  for (int c = 0; c < pk.P; c++) tr.write_scalar(ev(id_sig + c, x));
+  for (int c = 0; c < pk.cs.P; c++) tr.write_scalar(ev(id_sig + c, x));
   for (int ci = 0; ci < ncirc; ci++)
-    for (int s = 0; s < pk.nsets; s++) {
+    for (int s = 0; s < pk.cs.nsets; s++) {
       tr.write_scalar(ev(id_z(ci) + s, x));
       tr.write_scalar(ev(id_z(ci) + s, x_next));
-      if (s + 1 < pk.nsets) tr.write_scalar(ev(id_z(ci) + s, x_last));
+      if (s + 1 < pk.cs.nsets) tr.write_scalar(ev(id_z(ci) + s, x_last));
     }
   for (int ci = 0; ci < ncirc; ci++)
-    for (int l = 0; l < pk.NL; l++) {  // product, product_next, A', A'_inv, S' (lookup/prover.rs:330-361)
+    for (int l = 0; l < pk.cs.NL; l++) {  // product, product_next, A', A'_inv, S' (lookup/prover.rs:330-361)
       const int zi = id_lk(ci) + 3 * l;
       tr.write_scalar(ev(zi, x));
       tr.write_scalar(ev(zi, x_next));
@@ -1598,7 +1548,7 @@ int ProofRun::openings_and_evals() {
       tr.write_scalar(ev(zi + 2, x));
     }
   for (int ci = 0; ci < ncirc; ci++)
-    for (int s = 0; s < pk.NS; s++) {
+    for (int s = 0; s < pk.cs.NS; s++) {
       tr.write_scalar(ev(id_sh(ci) + s, x));
       tr.write_scalar(ev(id_sh(ci) + s, x_next));
     }
@@ -1663,7 +1613,7 @@ int prove_impl(Device* d, Params& prm, ProvingKey& pk, const ProveIn& in, std::v
                       g_spmd_colshard && g_spmd.world >= kColshardMinWorld && g_spmd.world > E_sub &&
                       g_spmd.world % E_sub == 0;
   if (spmd_subcosets()) RCCHK(sub_prepare(pk, st, pieces));  // this rank's sub-cosets of the key's cosets
-  const bool xsplit = g_spmd.world <= 1 && !spmd_subcosets() && pk.NL + pk.NS > 0;
+  const bool xsplit = g_spmd.world <= 1 && !spmd_subcosets() && pk.cs.NL + pk.cs.NS > 0;
   if (xsplit && !d->xstream) {  // after the MSM streams (h2g_init): the hardware-queue order, abi.cpp
     HIPCHK(hipStreamCreateWithFlags(&d->xstream, hipStreamNonBlocking));
     HIPCHK(hipEventCreateWithFlags(&d->xev_in, hipEventDisableTiming));
@@ -1685,22 +1635,22 @@ int prove_impl(Device* d, Params& prm, ProvingKey& pk, const ProveIn& in, std::v
 // the checks and output handling every create_proof entry point shares
 int create_proof_entry(Device* d, uint64_t params, uint64_t pk, ProveIn& in, uint8_t* proof, size_t proof_cap,
                        size_t* proof_len) {
-  auto ip = g_params.find(params);
-  if (ip == g_params.end()) return fail(H2G_ERR_HANDLE, "unknown params");
-  auto ik = g_pks.find(pk);
-  if (ik == g_pks.end()) return fail(H2G_ERR_HANDLE, "unknown proving key");
-  ProvingKey& K = *ik->second;
+  Params* ip = find_params(params);
+  if (!ip) return fail(H2G_ERR_HANDLE, "unknown params");
+  ProvingKey* ik = find_pk(pk);
+  if (!ik) return fail(H2G_ERR_HANDLE, "unknown proving key");
+  ProvingKey& K = *ik;
   if (K.params != params) return fail(H2G_ERR_ARG, "create_proof: pk was generated with other params");
   if (K.device != d->id) return fail(H2G_ERR_ARG, "create_proof: pk lives on another device");
   if (!proof_len || in.nc < 1 || in.nc > 1024) return fail(H2G_ERR_ARG, "create_proof: bad arguments");
   for (int c = 0; c < in.nc; c++) {
-    if (K.A && !in.src && !in.src1 && (!in.advice || !in.advice[c])) return fail(H2G_ERR_ARG, "create_proof: null advice");
-    if (K.I && (!in.instance || !in.inst_lens || !in.instance[c] || !in.inst_lens[c]))
+    if (K.cs.A && !in.src && !in.src1 && (!in.advice || !in.advice[c])) return fail(H2G_ERR_ARG, "create_proof: null advice");
+    if (K.cs.I && (!in.instance || !in.inst_lens || !in.instance[c] || !in.inst_lens[c]))
       return fail(H2G_ERR_ARG, "create_proof: null instance");  // InvalidInstances
   }
   std::vector<uint8_t> out;
   out.reserve(32 * 256);
-  int rc = prove_impl(d, *ip->second, K, in, &out);
+  int rc = prove_impl(d, *ip, K, in, &out);
   if (rc) {
     (void)hipStreamSynchronize(d->stream);
     return rc;

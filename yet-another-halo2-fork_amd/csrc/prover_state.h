@@ -158,48 +158,38 @@ struct CircuitWs {
 struct ProvingKey {
   int device = 0;
   uint64_t params = 0;
-  uint32_t k = 0;
+  // the circuit's shape (k, the column and argument counts, queries, phases, degree, blinding
+  // factors: read as pk.cs.X) and its expression graph, which h2g_vk_from_pk hands on
+  CsHost cs;
   size_t n = 0, ext = 0;
   uint64_t rot_scale = 0;
-  int degree = 0, bf = 0, P = 0, nsets = 0, chunk_len = 0;
-  int A = 0, F = 0, I = 0;
-  std::vector<Query> adv_q, fix_q, ins_q;
-  std::vector<std::pair<int, int>> perm_cols;
   std::vector<uint8_t> unblinded;
-  // advice_column_phase, challenge_phase (ConstraintSystemMid); challenge values live in
-  // consts[num_consts ..]
-  std::vector<uint8_t> adv_phase, ch_phase;
-  int num_consts = 0, max_phase = 0;
-  Fr transcript_repr;
+  int num_consts = 0;  // challenge values live in consts[num_consts ..]
   // verifying-key commitments (fixed, permutation) of a key read from bytes; a key made
   // by keygen computes them when it is written (h2g_pk_write)
   std::vector<G1Affine> vk_fixed, vk_perm;
-  CsHost cs;  // the host copy of the constraint system (h2g_vk_from_pk)
   // multi-open scheme of create_proof (the Prover type parameter, prover.rs:19-36):
   // 0 ProverSHPLONK, 1 ProverGWC; GWC witness polynomials, one per opening point
   int multiopen = 0;
   int transcript = 0;  // TRANSCRIPT_BLAKE2B / TRANSCRIPT_KECCAK256 (transcript.h)
   std::vector<Fr*> gwc_q;
-  uint32_t* lk_cnt = nullptr;  // pinned per-(circuit, lookup) match counters (LKC each)
-  size_t lk_cnt_len = 0;
-  // per-(circuit, lookup) device counters and table-row flags of the match, so that one
-  // memset each clears every lookup's and one copy brings all counters back
   static constexpr int LKC = 8;
   // the lookups' gathers and matches on LKS streams (lookup j's on stream j mod LKS), each
-  // stream with its own scratch set; set 0 is the one above (ck_a2 ... rep_rows, lkb_scr)
+  // stream with its own scratch set (of the key's blinding-row count: allocated once, by the
+  // first proof that uses them); set 0 is the key's own (ck_a2 ... rep_rows, lkb_scr)
   static constexpr int LKS = 4;
-  hipStream_t lk_st[LKS] = {};
-  hipEvent_t lk_ev[LKS + 1] = {};
+  Stream lk_st[LKS];
+  Event lk_ev[LKS + 1];
   CanonKey *lks_a2[LKS] = {}, *lks_t2[LKS] = {}, *lks_left[LKS] = {};
   uint8_t* lks_rep[LKS] = {};
   uint32_t* lks_rows[LKS] = {};
   void* lks_scr[LKS] = {};
-  size_t lks_n = 0;
-  uint32_t* lk_counters = nullptr;
-  uint8_t* lk_flags = nullptr;
-  size_t lk_cf_n = 0, lk_cf_u = 0;
-  Fr* lk_diff = nullptr;  // the lookup commitments' prefix-basis scalars (2 per lookup and circuit)
-  size_t lk_diff_len = 0;
+  // per-(circuit, lookup) device counters (LKC each) and table-row flags of the match, so
+  // that one memset each clears every lookup's and one copy brings all counters back
+  PinArr<uint32_t> lk_cnt;  // pinned per-(circuit, lookup) match counters (LKC each)
+  DevArr<uint32_t> lk_counters;
+  DevArr<uint8_t> lk_flags;
+  DevArr<Fr> lk_diff;  // the lookup commitments' prefix-basis scalars (2 per lookup and circuit)
   // permute_expression_pair's sort, chosen per lookup from the value width lk_hb[l] (bit
   // length of the largest canonical value) seen by the previous proof: <= 64 bits: radix
   // sort of the values themselves; wider: radix sort of a 48-bit window of the top bits
@@ -207,19 +197,19 @@ struct ProvingKey {
   // values.  lk_or_* (device / pinned, LKF per lookup): the limbs' OR and the check flag.
   static constexpr int LKF = 5;
   std::vector<int> lk_hb;
-  unsigned long long *lk_or_d = nullptr, *lk_or_h = nullptr;
-  size_t lk_or_len = 0;  // (circuit, lookup) entries of lk_or_*
+  DevArr<unsigned long long> lk_or_d;
+  PinArr<unsigned long long> lk_or_h;
   // SPMD witness checksums of an advice phase (copy_columns), device / pinned, and the event
   // that their copy to the host has landed (spmd_witness_fold)
-  unsigned long long *wsum_d = nullptr, *wsum_h = nullptr;
-  size_t wsum_len = 0;
-  hipEvent_t wsum_ev = nullptr;
+  DevArr<unsigned long long> wsum_d;
+  PinArr<unsigned long long> wsum_h;
+  Event wsum_ev;
   // pinned staging of a proof's small host-to-device uploads (blinding rows, seeds, staged
   // scalars; pk_upload): from pageable memory a hipMemcpyAsync costs 8-60 us of host time
   // (a staged copy), which left the GPU idle between the keccak-style circuit's 32 advice
   // columns; from pinned memory the copy is queued at once.  Re-armed per proof
-  uint8_t* up_h = nullptr;
-  size_t up_len = 0, up_off = 0;
+  PinArr<uint8_t> up_h;
+  size_t up_off = 0;
   Domain dom;
   Pool pool;
   // proving key (device)
@@ -242,7 +232,6 @@ struct ProvingKey {
   std::vector<Query> loads;  // the programs' load table (column, rotation)
   int* d_load_rot = nullptr;
   const Fr** d_sigma = nullptr;
-  int NL = 0, NS = 0;  // lookups, shuffles
   Fr *tmp_a = nullptr, *tmp_b = nullptr, *one = nullptr;
   CanonKey *ck_a2 = nullptr, *ck_t2 = nullptr, *ck_left = nullptr;
   uint8_t *rep_flag = nullptr, *left_flag = nullptr;
@@ -251,7 +240,10 @@ struct ProvingKey {
   std::vector<std::unique_ptr<CircuitWs>> cws;
   Fr *mod = nullptr, *pre = nullptr, *scr = nullptr, *random_poly = nullptr, *h_ext = nullptr, *h_coeff = nullptr;
   Fr *h_poly = nullptr, *nx = nullptr, *q1 = nullptr, *hx = nullptr, *lx = nullptr;
-  Fr *small = nullptr, *last_z = nullptr, *evals = nullptr, *eval_scr = nullptr;
+  Fr *small = nullptr, *last_z = nullptr;
+  // the evaluation batches' requests, results and scratch (openings_and_evals, slab_carries)
+  DevArr<EvalReq> d_reqs;
+  DevArr<Fr> evals, eval_scr;
   // SPMD sub-coset split (h2g_spmd_transport.bcast): this rank's sub-cosets t = rank,
   // rank + world, ... < 2^e of the extended domain; the key's cosets cut to them (slot i
   // of each buffer = sub-coset sub_ts[i]), per-slot sigma tables, and the 2^e x n slots
@@ -264,53 +256,42 @@ struct ProvingKey {
   bool sub_pieces = false;
   uint64_t sub_lo = 0, sub_hi = 0;
   int rot_lo = -1, rot_hi = 1;
-  Fr* cs_scr = nullptr;  // column ownership: the owned columns' 2^e sub-cosets
-  size_t cs_scr_len = 0;
-  Fr* perm_lz = nullptr;  // slab-wise grand products: z at each set's slab start
-  size_t perm_lz_len = 0;
+  DevArr<Fr> cs_scr;   // column ownership: the owned columns' 2^e sub-cosets
+  DevArr<Fr> perm_lz;  // slab-wise grand products: z at each set's slab start
   std::vector<Fr*> sub_fixed, sub_sigma;
   Fr *sub_l0 = nullptr, *sub_ll = nullptr, *sub_la = nullptr;
   std::vector<const Fr**> d_sigma_sub;
   Fr* h_gather = nullptr;
-  size_t scr_len = 0, eval_scr_len = 0;
-  EvalReq* d_reqs = nullptr;
-  int max_reqs = 0;
+  size_t scr_len = 0;  // of scr (allocated at keygen)
   // permute_expression_pair's batched sort: every lookup column's canonical values, keys
   // and row indices (ping-pong pairs), radix / compaction scratch
-  CanonKey* lkb_canon = nullptr;
-  uint64_t* lkb_key[2] = {nullptr, nullptr};
-  uint32_t* lkb_idx[2] = {nullptr, nullptr};
-  void* lkb_scr = nullptr;
-  size_t lkb_len = 0;
+  DevArr<CanonKey> lkb_canon;
+  DevArr<uint64_t> lkb_key[2];
+  DevArr<uint32_t> lkb_idx[2];
+  DevBuf lkb_scr;
   // SPMD coefficient slabs: per SHPLONK point a (slab + halo) combination buffer
-  Fr* slab_buf = nullptr;
-  size_t slab_buf_len = 0;
+  DevArr<Fr> slab_buf;
   // SPMD h(X) by slabs (h2g_spmd_transport.exchange): send / receive staging
-  Fr *x_send = nullptr, *x_recv = nullptr;
-  size_t x_send_len = 0, x_recv_len = 0;
+  DevArr<Fr> x_send, x_recv;
   // SPMD column ownership: the pack / unpack copy lists (host lists live until the next
   // stage, after a stream synchronisation, so their asynchronous uploads have completed)
-  CopySeg* d_segs = nullptr;
-  size_t d_segs_len = 0;
+  DevArr<CopySeg> d_segs;
   std::vector<CopySeg> h_segs[2];
   // overlapped column-ownership exchanges (h2g_set_spmd_exchange_async), in posting order:
   // each its own send / receive staging (grow-only, reused by the same position in the
   // next proof), completion event and unpack list, live from its post until xp_flush
   struct XPending {
-    Fr *send = nullptr, *recv = nullptr;
-    size_t send_len = 0, recv_len = 0;
-    hipEvent_t done = nullptr;
+    DevArr<Fr> send, recv;
+    Event done;
     std::vector<CopySeg> unpack;
     bool live = false;
   };
-  std::vector<XPending> xp;
+  std::vector<XPending> xp, xp_lost;  // xp_lost: abandoned by xp_drain, kept until the key goes
   size_t xp_used = 0;
   // a stage's blinding rows, uploaded in one copy (upload_rows_batch)
-  Fr* blind_d = nullptr;
-  size_t blind_d_len = 0;
-  uint32_t* d_seeds = nullptr;
-  uint64_t* d_offsets = nullptr;
-  int max_chunks = 0;
+  DevArr<Fr> blind_d;
+  DevArr<uint32_t> d_seeds;  // the vanishing argument's chunk seeds (8 words each) and offsets
+  DevArr<uint64_t> d_offsets;
   // the keystream position of the vanishing argument's seed draws in the last proof with
   // the seeded RNG (the draws before them depend on the circuit's shape only), and its
   // thread count: the next proof generates and commits the random polynomial early
@@ -320,8 +301,7 @@ struct ProvingKey {
   // buffer and counters, the blinding rows' generator inputs and values, the full sort's
   // keys / indices / scratch and its two sorted outputs, the copy list and column table
   struct CheckWs {
-    uint4* rec = nullptr;
-    size_t rec_cap = 0;
+    DevArr<uint4> rec;
     unsigned long long* total = nullptr;  // [0] the failure count, [1..9) lookup_keys / lookup_gather masks
     uint32_t* sh_flags = nullptr;         // one per shuffle
     uint32_t* seeds = nullptr;
@@ -333,11 +313,21 @@ struct ProvingKey {
     void* scr = nullptr;
     bool sort_ready = false;
     const Fr** cols = nullptr;
-    int32_t* copies = nullptr;
-    size_t copies_cap = 0;
+    DevArr<int32_t> copies;  // 6 words per copy constraint
     CopySeg* segs = nullptr;
     bool ready = false;
   } ck;
+  // Destruction.  h2g_pk_free synchronises the device stream and drains the overlapped
+  // exchanges first; the destructor waits for the lookup streams (a proof that failed
+  // between their fork and join leaves them running) before any member goes.  The members
+  // then go in reverse order of declaration: the buffers (ck ... lk_cnt) and `pool`
+  // before the events and streams that were declared above them (lk_ev, lk_st), so no
+  // stream is destroyed with work queued on a buffer, and no buffer freed under a stream
+  // that was not waited for.  A key that keygen or a read gives up on goes the same way.
+  ~ProvingKey() {
+    for (Stream& s : lk_st)
+      if (s) (void)hipStreamSynchronize(s);
+  }
 };
 
 // VerifyingKey (plonk.rs:42-231) as the verifier needs it: the constraint system and the
@@ -350,6 +340,16 @@ extern std::map<uint64_t, std::unique_ptr<VerifyingKey>> g_vks;   // verifier.cp
 
 extern std::map<uint64_t, std::unique_ptr<Params>> g_params;      // params.cpp
 extern std::map<uint64_t, std::unique_ptr<ProvingKey>> g_pks;     // keygen.cpp
+
+// the object behind a handle, or null
+template <class M>
+auto find_handle(M& m, uint64_t h) -> decltype(m.begin()->second.get()) {
+  auto it = m.find(h);
+  return it == m.end() ? nullptr : it->second.get();
+}
+inline Params* find_params(uint64_t h) { return find_handle(g_params, h); }
+inline ProvingKey* find_pk(uint64_t h) { return find_handle(g_pks, h); }
+inline VerifyingKey* find_vk(uint64_t h) { return find_handle(g_vks, h); }
 
 inline Fr fr_neg_one() { return Fr::zero() - Fr::one(); }
 
@@ -492,6 +492,8 @@ bool g2_valid(const G2Affine& a);
 
 // prover.cpp
 hipError_t pk_upload(ProvingKey& pk, void* dst, const void* src, size_t bytes, hipStream_t st);
+// a copy list in one launch: `segs` goes up into pk.d_segs (host list valid until st is synchronised)
+int copy_list_run(ProvingKey& pk, const std::vector<CopySeg>& segs, hipStream_t st);
 
 }  // namespace prv
 }  // namespace h2g

@@ -5,11 +5,13 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <cstring>
 #include <map>
 #include <memory>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/h2g.h"
@@ -38,25 +40,69 @@ int hip_fail(hipError_t e, const char* what);
     if (_rc) return _rc;    \
   } while (0)
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  hipError_t ensure(size_t bytes) {
-    if (bytes <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
+// Grow-only array of T in device memory (kPinned: in pinned host memory), owned by its
+// holder: freed when the holder goes, and when a larger one replaces it.  ensure() is a
+// compare on the warm path.  Growth waits for the device first -- kernels and copies in
+// flight may still read the old allocation, and that they have finished must not rest on
+// what hipFree happens to do -- so an address taken from `p` does not outlive the next
+// ensure(): size first, then take pointers.
+template <class T, bool kPinned = false>
+struct DevArr {
+  T* p = nullptr;
+  size_t len = 0;
+  DevArr() = default;
+  DevArr(DevArr&& o) noexcept : p(o.p), len(o.len) { o.p = nullptr, o.len = 0; }
+  DevArr& operator=(DevArr&& o) noexcept {
+    std::swap(p, o.p);
+    std::swap(len, o.len);
+    return *this;
+  }
+  ~DevArr() { release(); }
+  hipError_t ensure(size_t count) { return count <= len ? hipSuccess : grow(count); }
+  void release() {
+    if (p) (void)(kPinned ? hipHostFree(p) : hipFree(p));
     p = nullptr;
-    cap = 0;
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e == hipSuccess) cap = bytes;
+    len = 0;
+  }
+  template <class U>
+  U* as() const { return reinterpret_cast<U*>(p); }
+
+ private:
+  hipError_t grow(size_t count) {
+    hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) return e;
+    release();
+    e = kPinned ? hipHostMalloc((void**)&p, count * sizeof(T), hipHostMallocDefault)
+                : hipMalloc((void**)&p, count * sizeof(T));
+    if (e == hipSuccess) len = count;
+    else p = nullptr;
     return e;
   }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
+};
+template <class T>
+using PinArr = DevArr<T, true>;
+using DevBuf = DevArr<uint8_t>;  // untyped scratch, sized in bytes
+
+// A stream / an event that its holder owns: created on first use, destroyed with the holder
+template <class H, hipError_t (*kDestroy)(H)>
+struct Handle {
+  H h = nullptr;
+  Handle() = default;
+  Handle(Handle&& o) noexcept : h(o.h) { o.h = nullptr; }
+  Handle& operator=(Handle&& o) noexcept {
+    std::swap(h, o.h);
+    return *this;
   }
-  template <class T>
-  T* as() const { return reinterpret_cast<T*>(p); }
+  ~Handle() {
+    if (h) (void)kDestroy(h);
+  }
+  operator H() const { return h; }
+};
+struct Stream : Handle<hipStream_t, hipStreamDestroy> {
+  hipError_t ensure() { return h ? hipSuccess : hipStreamCreateWithFlags(&h, hipStreamNonBlocking); }
+};
+struct Event : Handle<hipEvent_t, hipEventDestroy> {
+  hipError_t ensure() { return h ? hipSuccess : hipEventCreateWithFlags(&h, hipEventDisableTiming); }
 };
 
 struct NttKey {  // omega, and the scale folded into the first pass's twiddles (ntt.h NttTables::fold)
@@ -76,15 +122,22 @@ struct Domain {
   uint32_t j = 0, k = 0, ek = 0;
   Fr omega, omega_inv, ext_omega, ext_omega_inv, g_coset, g_coset_inv, ifft_div, ext_ifft_div, bary;
   std::vector<Fr> t_evals;
-  Fr* d_t = nullptr;
+  DevArr<Fr> d_t;
 };
 
 struct Descriptor {
-  int device;
-  void* d = nullptr;  // scalars, or bases (= window 0 of fb.table when present)
+  int device = 0;
+  void* d = nullptr;  // scalars (= mem.p), or bases (= window 0 of fb.table)
   size_t n = 0;
   bool is_base = false;
-  MsmFixedBase fb;    // fixed-base windows of resident bases (owned: d aliases fb.table)
+  DevBuf mem;         // the scalars, or bases too few for windows
+  MsmFixedBase fb;    // fixed-base windows of resident bases (owned)
+  Descriptor() = default;
+  Descriptor(Descriptor&& o) noexcept
+      : device(o.device), d(o.d), n(o.n), is_base(o.is_base), mem(std::move(o.mem)), fb(o.fb) {
+    o.fb = MsmFixedBase{};
+  }
+  ~Descriptor() { msm_fixed_base_free(&fb); }
 };
 
 // Asynchronous fixed-base MSMs: whole MSMs on two streams with a workspace each, so that
@@ -145,8 +198,8 @@ Fr fr_delta();
 constexpr uint32_t FR_S = 28;
 
 int domain_init(Domain* dm, uint32_t j, uint32_t k);  // host constants + device t-evaluations
-void domain_release(Domain* dm);
-Domain* get_dom(uint64_t h);
+Domain* get_dom(uint64_t h);  // null: no such handle (find_desc, and prover_state.h find_*, alike)
+Descriptor* find_desc(uint64_t h);
 
 int get_tables(Device* d, const Fr& omega, int L, hipStream_t st, NttTables* out, const Fr& fold = Fr::one());
 int msm_dev_impl(Device* d, const void* sc, const void* bs, size_t n, int c, void* out, hipStream_t st);

@@ -124,7 +124,7 @@ int sub_prepare(ProvingKey& pk, hipStream_t st, bool pieces) {
   }
   // the rows a piece reads around its own: every query rotation, z(omega X), z(omega^last X),
   // the lookups' A'(omega^-1 X)
-  pk.rot_lo = std::min(-1, -(pk.bf + 1));
+  pk.rot_lo = std::min(-1, -(pk.cs.bf + 1));
   pk.rot_hi = 1;
   for (const Query& q : pk.loads) {
     pk.rot_lo = std::min(pk.rot_lo, q.rot);
@@ -136,17 +136,17 @@ int sub_prepare(ProvingKey& pk, hipStream_t st, bool pieces) {
     for (size_t i = 0; i < nt; i++) HIPCHK(subcoset_gather(full, *out + i * n, n, pk.sub_ts[i], e, st));
     return H2G_OK;
   };
-  pk.sub_fixed.resize(pk.F, nullptr);
-  pk.sub_sigma.resize(pk.P, nullptr);
-  for (int f = 0; f < pk.F; f++) RCCHK(cut(pk.fixed_coset[f], &pk.sub_fixed[f]));
-  for (int c = 0; c < pk.P; c++) RCCHK(cut(pk.sigma_coset[c], &pk.sub_sigma[c]));
+  pk.sub_fixed.resize(pk.cs.F, nullptr);
+  pk.sub_sigma.resize(pk.cs.P, nullptr);
+  for (int f = 0; f < pk.cs.F; f++) RCCHK(cut(pk.fixed_coset[f], &pk.sub_fixed[f]));
+  for (int c = 0; c < pk.cs.P; c++) RCCHK(cut(pk.sigma_coset[c], &pk.sub_sigma[c]));
   RCCHK(cut(pk.l0, &pk.sub_l0));
   RCCHK(cut(pk.l_last, &pk.sub_ll));
   RCCHK(cut(pk.l_active, &pk.sub_la));
   pk.d_sigma_sub.assign(nt, nullptr);
   for (size_t i = 0; i < nt; i++) {
-    std::vector<const Fr*> sg(pk.P + 1, nullptr);
-    for (int c = 0; c < pk.P; c++) sg[c] = pk.sub_sigma[c] + i * n;
+    std::vector<const Fr*> sg(pk.cs.P + 1, nullptr);
+    for (int c = 0; c < pk.cs.P; c++) sg[c] = pk.sub_sigma[c] + i * n;
     PALLOC(pk.pool, pk.d_sigma_sub[i], sg.size());
     HIPCHK(hipMemcpy(pk.d_sigma_sub[i], sg.data(), sg.size() * sizeof(Fr*), hipMemcpyHostToDevice));
   }
@@ -170,14 +170,14 @@ int sub_ws_tables(const ProvingKey& pk, CircuitWs& w) {
     };
     std::vector<const Fr*> lc(pk.n_loads + 1, nullptr);
     for (int j = 0; j < pk.n_loads; j++) lc[j] = col(pk.loads[j]);
-    std::vector<EvalLookup> el(pk.NL + 1);
-    std::vector<EvalShuffle> es(pk.NS + 1);
-    for (int l = 0; l < pk.NL; l++)
+    std::vector<EvalLookup> el(pk.cs.NL + 1);
+    std::vector<EvalShuffle> es(pk.cs.NS + 1);
+    for (int l = 0; l < pk.cs.NL; l++)
       el[l] = EvalLookup{pk.seg_lk_in[l], pk.seg_lk_tab[l], w.lk_zc[l] + off, w.lk_apc[l] + off, w.lk_spc[l] + off};
-    for (int l = 0; l < pk.NS; l++) es[l] = EvalShuffle{pk.seg_sh_in[l], pk.seg_sh_sh[l], w.sh_zc[l] + off};
-    std::vector<const Fr*> zt(pk.nsets + 1, nullptr), pv(pk.P + 1, nullptr);
-    for (int q = 0; q < pk.nsets; q++) zt[q] = w.z_coset[q] + off;
-    for (int c = 0; c < pk.P; c++) pv[c] = col(Query{pk.perm_cols[c].first, pk.perm_cols[c].second, 0});
+    for (int l = 0; l < pk.cs.NS; l++) es[l] = EvalShuffle{pk.seg_sh_in[l], pk.seg_sh_sh[l], w.sh_zc[l] + off};
+    std::vector<const Fr*> zt(pk.cs.nsets + 1, nullptr), pv(pk.cs.P + 1, nullptr);
+    for (int q = 0; q < pk.cs.nsets; q++) zt[q] = w.z_coset[q] + off;
+    for (int c = 0; c < pk.cs.P; c++) pv[c] = col(Query{pk.cs.perm_cols[c].first, pk.cs.perm_cols[c].second, 0});
     CircuitWs::SubTables& S = w.sub[i];
     PALLOC(w.pool, S.load_col, lc.size());
     PALLOC(w.pool, S.lookups, el.size());
@@ -231,7 +231,7 @@ int h_by_slabs(Device* d, ProvingKey& pk, const Slab& sl, hipStream_t st) {
   const int W = g_spmd.world, me = g_spmd.rank;
   const int e = (int)(D.ek - D.k);
   const int E = 1 << e;
-  const int np = pk.degree - 1;
+  const int np = pk.cs.degree - 1;
   if (E > HSLAB_MAX_E || np > E) return fail(H2G_ERR_ARG, "create_proof: too many sub-cosets for the h slab exchange");
   // the sub-cosets this rank interpolates (with row pieces: the leaders, ranks < E)
   std::vector<uint64_t> ts = pk.sub_ts;
@@ -250,14 +250,8 @@ int h_by_slabs(Device* d, ProvingKey& pk, const Slab& sl, hipStream_t st) {
   }
   size_t rtot = 0;
   for (int r = 0; r < W; r++) rtot += rb[r] / sizeof(Fr);
-  if (soff[W] > pk.x_send_len) {
-    PALLOC(pk.pool, pk.x_send, soff[W]);
-    pk.x_send_len = soff[W];
-  }
-  if (rtot > pk.x_recv_len) {
-    PALLOC(pk.pool, pk.x_recv, rtot);
-    pk.x_recv_len = rtot;
-  }
+  HIPCHK(pk.x_send.ensure(soff[W]));
+  HIPCHK(pk.x_recv.ensure(rtot));
   const Fr one = Fr::one();
   for (size_t i = 0; i < nt; i++) {
     const uint64_t t = ts[i];
@@ -268,7 +262,7 @@ int h_by_slabs(Device* d, ProvingKey& pk, const Slab& sl, hipStream_t st) {
     for (int r = 0; r < W; r++) {
       const size_t cnt = slabs[r].hi1 - slabs[r].lo;
       if (cnt)
-        HIPCHK(hipMemcpyAsync(pk.x_send + soff[r] + i * cnt, f + slabs[r].lo, cnt * sizeof(Fr), hipMemcpyDeviceToDevice,
+        HIPCHK(hipMemcpyAsync(pk.x_send.p + soff[r] + i * cnt, f + slabs[r].lo, cnt * sizeof(Fr), hipMemcpyDeviceToDevice,
                               st));
     }
   }
@@ -293,10 +287,10 @@ int h_by_slabs(Device* d, ProvingKey& pk, const Slab& sl, hipStream_t st) {
   }
   HIPCHK(pk_upload(pk, pk.small, coef.data(), coef.size() * sizeof(Fr), st));
   HIPCHK(hipStreamSynchronize(st));  // the send staging is complete; coef (host) was read
-  if (spmd_exchange(pk.x_send, sb.data(), pk.x_recv, rb.data()) != 0)
+  if (spmd_exchange(pk.x_send.p, sb.data(), pk.x_recv.p, rb.data()) != 0)
     return fail(H2G_ERR_STATE, "spmd transport: exchange of h slabs failed");
   HSlabArgs a;
-  a.recv = pk.x_recv;
+  a.recv = pk.x_recv.p;
   int pos = 0;
   for (int o = 0; o < W; o++)
     for (int t = o; t < E; t += W) a.idx[t] = pos++;
@@ -334,34 +328,28 @@ int coef_exchange(ProvingKey& pk, const std::vector<Fr*>& cols, hipStream_t st) 
     stot += sb[r] / sizeof(Fr);
     rtot += rb[r] / sizeof(Fr);
   }
-  if (stot > pk.x_send_len) {
-    PALLOC(pk.pool, pk.x_send, stot);
-    pk.x_send_len = stot;
-  }
-  if (rtot > pk.x_recv_len) {
-    PALLOC(pk.pool, pk.x_recv, rtot);
-    pk.x_recv_len = rtot;
-  }
+  HIPCHK(pk.x_send.ensure(stot));
+  HIPCHK(pk.x_recv.ensure(rtot));
   if (me < E) {  // pack: per destination, my columns' slabs
     size_t off = 0;
     for (int r = E; r < W; r++) {
       const size_t cnt = slabs[r].hi1 - slabs[r].lo;
       for (int c = me; c < nc; c += E) {
-        if (cnt) HIPCHK(hipMemcpyAsync(pk.x_send + off, cols[c] + slabs[r].lo, cnt * sizeof(Fr),
+        if (cnt) HIPCHK(hipMemcpyAsync(pk.x_send.p + off, cols[c] + slabs[r].lo, cnt * sizeof(Fr),
                                        hipMemcpyDeviceToDevice, st));
         off += cnt;
       }
     }
   }
   HIPCHK(hipStreamSynchronize(st));
-  if (spmd_exchange(pk.x_send, sb.data(), pk.x_recv, rb.data()) != 0)
+  if (spmd_exchange(pk.x_send.p, sb.data(), pk.x_recv.p, rb.data()) != 0)
     return fail(H2G_ERR_STATE, "spmd transport: exchange of coefficient slabs failed");
   if (me >= E) {  // unpack: owner by owner, its columns in order
     const size_t cnt = slabs[me].hi1 - slabs[me].lo;
     size_t off = 0;
     for (int o = 0; o < E; o++)
       for (int c = o; c < nc; c += E) {
-        if (cnt) HIPCHK(hipMemcpyAsync(cols[c] + slabs[me].lo, pk.x_recv + off, cnt * sizeof(Fr),
+        if (cnt) HIPCHK(hipMemcpyAsync(cols[c] + slabs[me].lo, pk.x_recv.p + off, cnt * sizeof(Fr),
                                        hipMemcpyDeviceToDevice, st));
         off += cnt;
       }
@@ -441,44 +429,17 @@ int colshard_distribute(Device* d, ProvingKey& pk, const std::vector<const Fr*>&
   if (g_xpost) {
     if (pk.xp_used == pk.xp.size()) pk.xp.emplace_back();
     xp = &pk.xp[pk.xp_used];
-    if (soff[W] > xp->send_len) {
-      PALLOC(pk.pool, xp->send, soff[W]);
-      xp->send_len = soff[W];
-    }
-    if (rtot > xp->recv_len) {
-      PALLOC(pk.pool, xp->recv, rtot);
-      xp->recv_len = rtot;
-    }
-    if (!xp->done) HIPCHK(hipEventCreateWithFlags(&xp->done, hipEventDisableTiming));
+    HIPCHK(xp->send.ensure(soff[W]));
+    HIPCHK(xp->recv.ensure(rtot));
+    HIPCHK(xp->done.ensure());
   } else {
-    if (soff[W] > pk.x_send_len) {
-      PALLOC(pk.pool, pk.x_send, soff[W]);
-      pk.x_send_len = soff[W];
-    }
-    if (rtot > pk.x_recv_len) {
-      PALLOC(pk.pool, pk.x_recv, rtot);
-      pk.x_recv_len = rtot;
-    }
+    HIPCHK(pk.x_send.ensure(soff[W]));
+    HIPCHK(pk.x_recv.ensure(rtot));
   }
-  Fr* const xs = xp ? xp->send : pk.x_send;
-  Fr* const xr = xp ? xp->recv : pk.x_recv;
-  const size_t scr = mine.size() * (size_t)E * n;
-  if (scr > pk.cs_scr_len) {
-    PALLOC(pk.pool, pk.cs_scr, scr);
-    pk.cs_scr_len = scr;
-  }
-  auto run_segs = [&](std::vector<CopySeg>& v) -> int {  // one launch for a copy list
-    if (v.empty()) return H2G_OK;
-    if (v.size() > pk.d_segs_len) {
-      PALLOC(pk.pool, pk.d_segs, v.size());
-      pk.d_segs_len = v.size();
-    }
-    uint64_t mx = 0;
-    for (const CopySeg& g : v) mx = std::max<uint64_t>(mx, g.len);
-    HIPCHK(pk_upload(pk, pk.d_segs, v.data(), v.size() * sizeof(CopySeg), st));
-    HIPCHK(copy_segments(pk.d_segs, (int)v.size(), mx, st));
-    return H2G_OK;
-  };
+  HIPCHK(pk.cs_scr.ensure(mine.size() * (size_t)E * n));
+  // (every buffer the copy lists below point into is sized by now)
+  Fr* const xs = xp ? xp->send.p : pk.x_send.p;
+  Fr* const xr = xp ? xp->recv.p : pk.x_recv.p;
   // rows [a, a + len) mod n of one sub-coset: one or two runs
   auto runs = [&](const RowPiece& pc, auto&& fn) {
     const uint64_t first = std::min<uint64_t>(pc.len, n - pc.a);
@@ -496,7 +457,7 @@ int colshard_distribute(Device* d, ProvingKey& pk, const std::vector<const Fr*>&
     RCCHK(lagrange_to_coeff_batch(d, pk.dom, l2.data(), p2.data(), (int)l2.size(), st));
     for (size_t q = 0; q < mine.size(); q++)
       for (int t = 0; t < E; t++) {
-        Fr* o = pk.cs_scr + (q * E + t) * n;
+        Fr* o = pk.cs_scr.p + (q * E + t) * n;
         HIPCHK(subcoset_twist(poly[mine[q]], o, n, pk.eo, (uint64_t)t, pk.ext - 1, st));
         io.push_back(o);
       }
@@ -515,7 +476,7 @@ int colshard_distribute(Device* d, ProvingKey& pk, const std::vector<const Fr*>&
     for (size_t q = 0; q < mine.size(); q++) {
       const int i = mine[q];
       for (const RowPiece& pc : pcs[r]) {
-        const Fr* src = pk.cs_scr + (q * E + pc.t) * n;
+        const Fr* src = pk.cs_scr.p + (q * E + pc.t) * n;
         runs(pc, [&](uint64_t row, uint64_t at, uint64_t cnt) {
           if (r == me) pack.push_back(CopySeg{src + row, coset[i] + (size_t)pc.slot * n + row, cnt});
           else pack.push_back(CopySeg{src + row, xs + pos + at, cnt});
@@ -544,11 +505,11 @@ int colshard_distribute(Device* d, ProvingKey& pk, const std::vector<const Fr*>&
       off += mycnt;
     }
   }
-  RCCHK(run_segs(pack));
+  RCCHK(copy_list_run(pk, pack, st));
   if (xp) {  // behind the pack on the stream; the receiver's rows land before h(X) (xp_flush)
     uint64_t bytes = 0;
     for (int r = 0; r < W; r++) bytes += sb[r] + rb[r];
-    if (spmd_timed(2, bytes, [&] { return g_xpost(g_spmd.ctx, xs, sb.data(), xr, rb.data(), st, xp->done); }) != 0)
+    if (spmd_timed(2, bytes, [&] { return g_xpost(g_spmd.ctx, xs, sb.data(), xr, rb.data(), st, xp->done.h); }) != 0)
       return fail(H2G_ERR_STATE, "spmd transport: exchange of column sub-cosets failed (post)");
     xp->unpack.swap(unpack);
     xp->live = true;
@@ -558,7 +519,7 @@ int colshard_distribute(Device* d, ProvingKey& pk, const std::vector<const Fr*>&
   HIPCHK(hipStreamSynchronize(st));
   if (spmd_exchange(xs, sb.data(), xr, rb.data()) != 0)
     return fail(H2G_ERR_STATE, "spmd transport: exchange of column sub-cosets failed");
-  RCCHK(run_segs(unpack));
+  RCCHK(copy_list_run(pk, unpack, st));
   return H2G_OK;
 }
 
@@ -578,16 +539,7 @@ int xp_flush(ProvingKey& pk, hipStream_t st) {
       return fail(H2G_ERR_STATE, "spmd transport: exchange of column sub-cosets failed (wait)");
     }
     HIPCHK(hipStreamWaitEvent(st, x.done, 0));
-    if (!x.unpack.empty()) {
-      if (x.unpack.size() > pk.d_segs_len) {
-        PALLOC(pk.pool, pk.d_segs, x.unpack.size());
-        pk.d_segs_len = x.unpack.size();
-      }
-      uint64_t mx = 0;
-      for (const CopySeg& g : x.unpack) mx = std::max<uint64_t>(mx, g.len);
-      HIPCHK(pk_upload(pk, pk.d_segs, x.unpack.data(), x.unpack.size() * sizeof(CopySeg), st));
-      HIPCHK(copy_segments(pk.d_segs, (int)x.unpack.size(), mx, st));
-    }
+    RCCHK(copy_list_run(pk, x.unpack, st));
   }
   pk.xp_used = 0;
   return H2G_OK;
@@ -595,9 +547,9 @@ int xp_flush(ProvingKey& pk, hipStream_t st) {
 
 // a failed proof's exchanges still in flight: wait for them before their staging is reused
 // or freed -- one bound for all of them together (10 s), and an exchange still pending past
-// it is abandoned, not reused: its staging and event are dropped (the key's pool releases
-// the memory with the key) so that the next proof posts into fresh buffers a late transfer
-// cannot write
+// it is abandoned, not reused: its staging and event move to xp_lost (released with the
+// key) so that the next proof posts into fresh buffers a late transfer cannot write
+// 
 void xp_drain(ProvingKey& pk) {
   const auto t0 = std::chrono::steady_clock::now();
   for (ProvingKey::XPending& x : pk.xp) {
@@ -607,10 +559,8 @@ void xp_drain(ProvingKey& pk) {
            std::chrono::steady_clock::now() - t0 < std::chrono::seconds(10))
       std::this_thread::sleep_for(std::chrono::microseconds(200));
     if (hipEventQuery(x.done) == hipErrorNotReady) {
-      x.send = x.recv = nullptr;
-      x.send_len = x.recv_len = 0;
-      x.done = nullptr;  // a new event for the next post (the pending one is left to the runtime)
-      x.unpack.clear();
+      pk.xp_lost.push_back(std::move(x));
+      x = ProvingKey::XPending{};
     }
   }
   pk.xp_used = 0;
@@ -661,14 +611,8 @@ int gather_to_owners(ProvingKey& pk, const std::vector<Fr*>& cols, const std::ve
   }
   size_t rtot = 0;
   for (int r = 0; r < W; r++) rtot += rb[r] / sizeof(Fr);
-  if (soff[W] > pk.x_send_len) {
-    PALLOC(pk.pool, pk.x_send, soff[W]);
-    pk.x_send_len = soff[W];
-  }
-  if (rtot > pk.x_recv_len) {
-    PALLOC(pk.pool, pk.x_recv, rtot);
-    pk.x_recv_len = rtot;
-  }
+  HIPCHK(pk.x_send.ensure(soff[W]));
+  HIPCHK(pk.x_recv.ensure(rtot));
   std::vector<CopySeg>& pack = pk.h_segs[0];
   std::vector<CopySeg>& unpack = pk.h_segs[1];
   pack.clear();
@@ -679,7 +623,7 @@ int gather_to_owners(ProvingKey& pk, const std::vector<Fr*>& cols, const std::ve
     size_t pos = soff[r];
     for (int i = 0; i < M; i++)
       if (owner[i] == r) {
-        pack.push_back(CopySeg{cols[i] + lo[me], pk.x_send + pos, my});
+        pack.push_back(CopySeg{cols[i] + lo[me], pk.x_send.p + pos, my});
         pos += my;
       }
   }
@@ -689,54 +633,35 @@ int gather_to_owners(ProvingKey& pk, const std::vector<Fr*>& cols, const std::ve
     const size_t cnt = lo[r + 1] - lo[r];
     for (int i = 0; i < M; i++)
       if (owner[i] == me && cnt) {
-        unpack.push_back(CopySeg{pk.x_recv + off, cols[i] + lo[r], cnt});
+        unpack.push_back(CopySeg{pk.x_recv.p + off, cols[i] + lo[r], cnt});
         off += cnt;
       }
   }
-  auto run = [&](std::vector<CopySeg>& v) -> int {
-    if (v.empty()) return H2G_OK;
-    if (v.size() > pk.d_segs_len) {
-      PALLOC(pk.pool, pk.d_segs, v.size());
-      pk.d_segs_len = v.size();
-    }
-    uint64_t mx = 0;
-    for (const CopySeg& g : v) mx = std::max<uint64_t>(mx, g.len);
-    HIPCHK(pk_upload(pk, pk.d_segs, v.data(), v.size() * sizeof(CopySeg), st));
-    HIPCHK(copy_segments(pk.d_segs, (int)v.size(), mx, st));
-    return H2G_OK;
-  };
-  RCCHK(run(pack));
+  RCCHK(copy_list_run(pk, pack, st));
   HIPCHK(hipStreamSynchronize(st));
-  if (spmd_exchange(pk.x_send, sb.data(), pk.x_recv, rb.data()) != 0)
+  if (spmd_exchange(pk.x_send.p, sb.data(), pk.x_recv.p, rb.data()) != 0)
     return fail(H2G_ERR_STATE, "spmd transport: exchange of product slabs failed");
-  RCCHK(run(unpack));
+  RCCHK(copy_list_run(pk, unpack, st));
   return H2G_OK;
 }
 
-// SPMD: an advice phase's m column checksums (pk.wsum_d, filled by the copy_columns that
+// SPMD: an advice phase's m column checksums (pk.wsum_d.p, filled by the copy_columns that
 // brought the columns in) to the host behind the stream; folded into the consistency
 // digest by the next collective (spmd_witness_settle) -- only when sharded
 int spmd_witness_prepare(ProvingKey& pk, int m, hipStream_t st) {
   if (g_spmd.world <= 1 || m <= 0) return H2G_OK;
   spmd_witness_settle();  // an earlier phase's, before its pinned buffer is reused
-  if ((size_t)m > pk.wsum_len) {
-    if (pk.wsum_d) (void)hipFree(pk.wsum_d);
-    if (pk.wsum_h) (void)hipHostFree(pk.wsum_h);
-    pk.wsum_d = pk.wsum_h = nullptr;
-    pk.wsum_len = 0;
-    HIPCHK(hipMalloc((void**)&pk.wsum_d, (size_t)m * sizeof(unsigned long long)));
-    HIPCHK(hipHostMalloc((void**)&pk.wsum_h, (size_t)m * sizeof(unsigned long long), hipHostMallocDefault));
-    pk.wsum_len = (size_t)m;
-  }
-  if (!pk.wsum_ev) HIPCHK(hipEventCreateWithFlags(&pk.wsum_ev, hipEventDisableTiming));
-  HIPCHK(hipMemsetAsync(pk.wsum_d, 0, (size_t)m * sizeof(unsigned long long), st));
+  HIPCHK(pk.wsum_d.ensure(m));
+  HIPCHK(pk.wsum_h.ensure(m));
+  HIPCHK(pk.wsum_ev.ensure());
+  HIPCHK(hipMemsetAsync(pk.wsum_d.p, 0, (size_t)m * sizeof(unsigned long long), st));
   return H2G_OK;
 }
 int spmd_witness_fold(ProvingKey& pk, int m, hipStream_t st) {
   if (g_spmd.world <= 1 || m <= 0) return H2G_OK;
-  HIPCHK(hipMemcpyAsync(pk.wsum_h, pk.wsum_d, (size_t)m * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(pk.wsum_h.p, pk.wsum_d.p, (size_t)m * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
   HIPCHK(hipEventRecord(pk.wsum_ev, st));
-  g_spmd_check.pend = pk.wsum_h;
+  g_spmd_check.pend = pk.wsum_h.p;
   g_spmd_check.pend_n = m;
   g_spmd_check.pend_ev = pk.wsum_ev;
   return H2G_OK;
@@ -905,10 +830,10 @@ int h2g_comm_spmd_uninstall(void) {
 
 int h2g_comm_install(uint64_t params) {
   NEED_DEV_P();
-  auto ip = g_params.find(params);
-  if (ip == g_params.end()) return fail(H2G_ERR_HANDLE, "unknown params");
+  Params* ip = find_params(params);
+  if (!ip) return fail(H2G_ERR_HANDLE, "unknown params");
   if (comm_world() < 2 || comm_rank() != 0) return fail(H2G_ERR_STATE, "comm_install: needs rank 0 of a communicator");
-  g_shard = h2g_shard_transport{comm_transport_ctx(ip->second->n), comm_world(), comm_launch, comm_collect};
+  g_shard = h2g_shard_transport{comm_transport_ctx(ip->n), comm_world(), comm_launch, comm_collect};
   g_shard_seq = 0;
   return H2G_OK;
 }
@@ -922,9 +847,9 @@ int h2g_comm_stop(void) {
 /* ranks 1..: answer rank 0's MSM slabs against `params` until it stops the session */
 int h2g_comm_serve(uint64_t params, uint64_t* served) {
   NEED_DEV_P();
-  auto ip = g_params.find(params);
-  if (ip == g_params.end()) return fail(H2G_ERR_HANDLE, "unknown params");
-  Params& prm = *ip->second;
+  Params* ip = find_params(params);
+  if (!ip) return fail(H2G_ERR_HANDLE, "unknown params");
+  Params& prm = *ip;
   if (prm.device != d->id) return fail(H2G_ERR_ARG, "comm_serve: params live on another device");
   static_assert(COMM_OP_STOP == commwait::REQ_STOP && COMM_OP_MSM == commwait::REQ_MSM &&
                     COMM_OP_PING == commwait::REQ_PING,

@@ -513,8 +513,8 @@ bool dual_check(const VerifierPoints& vp, const G1Affine& l, const G1Affine& r) 
 int verify_impl(Device* d, uint64_t vk_h, const h2g_verifier_params* vpp, int multiopen, int transcript,
                 const h2g_verify_item* items, size_t count, const h2g_rng* rng, bool combine, int32_t* verdicts,
                 uint64_t stats[4]) {
-  auto it = g_vks.find(vk_h);
-  if (it == g_vks.end()) return fail(H2G_ERR_HANDLE, "unknown verifying key");
+  VerifyingKey* it = find_vk(vk_h);
+  if (!it) return fail(H2G_ERR_HANDLE, "unknown verifying key");
   if (multiopen != MULTIOPEN_SHPLONK && multiopen != MULTIOPEN_GWC)
     return fail(H2G_ERR_ARG, "verify: multiopen must be 0 (SHPLONK) or 1 (GWC)");
   if (transcript != TRANSCRIPT_BLAKE2B && transcript != TRANSCRIPT_KECCAK256)
@@ -523,7 +523,7 @@ int verify_impl(Device* d, uint64_t vk_h, const h2g_verifier_params* vpp, int mu
   // an installed shard or SPMD transport takes no part: nothing here goes through commit()
   VerifierPoints vp;
   RCCHK(load_vp(vpp, &vp));
-  const VerifyingKey& vk = *it->second;
+  const VerifyingKey& vk = *it;
   hipStream_t st = d->stream;
   double t_host = 0, t_dec = 0, t_msm = 0, t_pair = 0;
   uint64_t n_checks = 0, n_terms = 0, n_points = 0;
@@ -722,13 +722,13 @@ extern "C" {
 int h2g_vk_from_pk(uint64_t pk_h, uint64_t* vk) {
   NEED_DEV_P();
   if (!vk) return fail(H2G_ERR_ARG, "vk_from_pk: null argument");
-  auto it = g_pks.find(pk_h);
-  if (it == g_pks.end()) return fail(H2G_ERR_HANDLE, "unknown proving key");
+  ProvingKey* it = find_pk(pk_h);
+  if (!it) return fail(H2G_ERR_HANDLE, "unknown proving key");
   RCCHK(h2g_pk_vk_commitments(pk_h, nullptr, nullptr));  // commit_lagrange, once per key
   auto key = std::make_unique<VerifyingKey>();
-  key->cs = it->second->cs;
-  key->fixed = it->second->vk_fixed;
-  key->perm = it->second->vk_perm;
+  key->cs = it->cs;
+  key->fixed = it->vk_fixed;
+  key->perm = it->vk_perm;
   *vk = g_next_handle++;
   g_vks[*vk] = std::move(key);
   return H2G_OK;
@@ -742,10 +742,10 @@ int h2g_vk_free(uint64_t vk) {
 
 int h2g_params_verifier(uint64_t params, h2g_verifier_params* out) {
   NEED_DEV_P();
-  auto it = g_params.find(params);
-  if (it == g_params.end()) return fail(H2G_ERR_HANDLE, "unknown params");
+  Params* it = find_params(params);
+  if (!it) return fail(H2G_ERR_HANDLE, "unknown params");
   if (!out) return fail(H2G_ERR_ARG, "params_verifier: null argument");
-  const Params& p = *it->second;
+  const Params& p = *it;
   if (!p.has_g2) return fail(H2G_ERR_STATE, "params_verifier: the params have no G2 points (h2g_params_set_g2)");
   HIPCHK(hipStreamSynchronize(d->stream));
   HIPCHK(hipMemcpy(out->g1, p.g, sizeof(G1Affine), hipMemcpyDeviceToHost));
@@ -779,9 +779,9 @@ int h2g_multiopen_verify(const h2g_verifier_params* vpp, int scheme, uint64_t tr
   NEED_DEV_P();
   if (!verdict) return fail(H2G_ERR_ARG, "multiopen_verify: null argument");
   *verdict = H2G_VERIFY_MALFORMED;
-  auto ti = g_transcripts.find(transcript);
-  if (ti == g_transcripts.end()) return fail(H2G_ERR_HANDLE, "unknown transcript");
-  TranscriptObj& T = *ti->second;
+  TranscriptObj* ti = find_transcript(transcript);
+  if (!ti) return fail(H2G_ERR_HANDLE, "unknown transcript");
+  TranscriptObj& T = *ti;
   if (scheme != MULTIOPEN_SHPLONK && scheme != MULTIOPEN_GWC)
     return fail(H2G_ERR_ARG, "multiopen_verify: scheme must be 0 (SHPLONK) or 1 (GWC)");
   if (!T.read) return fail(H2G_ERR_ARG, "multiopen_verify: a write-mode transcript");
