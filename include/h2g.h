@@ -589,6 +589,40 @@ int h2g_multiopen_verify(const h2g_verifier_params* vp, int scheme, uint64_t tra
                          const uint64_t* commitments, size_t ncommitments,
                          const h2g_verify_query* queries, size_t nqueries, int32_t* verdict, uint64_t lr[16]);
 
+/* ---- the pairing check on the device (csrc/pairing_dev.hip): every input's verdict in one
+ * launch, for a failing batch and for a host that deferred the pairings of many
+ * h2g_multiopen_verify calls.  Both G2 arguments are the params' fixed points, so the host
+ * builds their Miller-loop lines once per (g2, s_g2) (kept with the device state, released by
+ * h2g_shutdown) and the device does no G2 arithmetic.  The final exponentiation goes through
+ * powers of u and raises to m (p^12 - 1) / r with m = 2u (6u^2 + 3u + 1), u = 0x44e992b44a6909f1;
+ * gcd(m, r) = 1, so "== 1" decides what the exact exponent decides.
+ * ok[i] = 1 iff e(left_i, s_g2) == e(right_i, g2); lr = count x 16 u64 (left[8], right[8],
+ * affine Montgomery, identity = zeros): the layout h2g_multiopen_verify writes.  A pair with
+ * the identity as its G1 point contributes 1, as on the host.
+ * The host entry validates vp (a G2 point outside the r-torsion is H2G_ERR_ARG) and every
+ * coordinate (below p, on the curve or the identity; H2G_ERR_ARG names the index and leaves ok
+ * untouched), copies in and out and returns when ok is ready; count == 0 is H2G_OK, count
+ * above 2^24 H2G_ERR_ARG.  One launch lasts about as long as one check's dependent chain
+ * (~6.6 ms on an MI355X) up to a few thousand checks. */
+int h2g_pairing_check_batch(const h2g_verifier_params* vp, const uint64_t* lr, size_t count, int32_t* ok);
+/* d_lr / d_ok (count x int32) in device memory, 16-byte aligned; asynchronous on `stream`
+ * (NULL: the library's).  The points are not validated: an input off the curve gets an
+ * unspecified verdict, never a fault.  d_lr is only read. */
+int h2g_pairing_check_batch_dev(const h2g_verifier_params* vp, const void* d_lr, size_t count,
+                                void* d_ok /* count x int32 */, void* stream);
+/* how h2g_verify_batch resolves a failing batch: 0 bisection (default, as before),
+ * 1 one device launch of per-proof checks over the resident (L_i, R_i): the combined check runs
+ * as in mode 0, and if it fails every well-formed proof gets the verdict h2g_verify_proof
+ * would give (these checks carry no random factor); stats[0] is then 1 + the number of
+ * well-formed proofs, whatever the number of bad ones.  Process-wide.  Another mode is
+ * H2G_ERR_ARG. */
+int h2g_verify_set_isolation(int mode);
+/* test seam: the values behind the verdicts, 48 u64 each (6 Fq2 coefficients of 1, w, .., w^5,
+ * Montgomery form): miller = f_{s_g2}(left) f_{g2}(-right), gt = its final value (the exact
+ * final exponentiation's, raised to m); either output may be NULL */
+int h2g_debug_pairing_values(const h2g_verifier_params* vp, const uint64_t* lr, size_t count,
+                             uint64_t* miller, uint64_t* gt);
+
 /* wall milliseconds of the stages of the last h2g_create_proof (names: h2g_prover_stage_name).
  * Stages end when their work is queued, unless h2g_prover_stage_sync(1) is set: then each
  * stage boundary synchronises the prover stream and the times are GPU completion times

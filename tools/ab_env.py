@@ -3,7 +3,8 @@
 
 Each variant runs in its own child process, variants alternate for `--reps` rounds, and
 the child measures lone fixed-base MSMs (2^log_n resident points, per-phase HIP-event
-times) and/or the C3 create_proof at k.  Prints one JSON line per child and a summary.
+times), the C3 create_proof at k and/or verify_batch over 256 valid proofs (--verify keccak:9).
+Prints one JSON line per child and a summary.
 
     python tools/ab_env.py --variants 'H2G_MSM_FINE=tile' '' --msm 19,21,22,24 --prove 22 --reps 2
 """
@@ -26,7 +27,7 @@ def child(args):
     import h2g
     import h2g_circuit as hc
     h2g.init([0])
-    out = {"msm": {}, "prove": {}}
+    out = {"msm": {}, "prove": {}, "verify": {}}
     rng = np.random.default_rng(1000)
     for ln in [int(x) for x in args.msm.split(",") if x]:
         n = 1 << ln
@@ -82,6 +83,28 @@ def child(args):
         pk.close()
         params.close()
         del adv
+    for spec in [x for x in args.verify.split(",") if x]:  # all-valid batch of 256: "keccak:9" or "c3:12"
+        kind, _, kk = spec.rpartition(":")
+        k = int(kk)
+        circ, wit = hc.keccak_style(k) if kind == "keccak" else hc.synthetic_c3(k, h2g.DeviceOps)
+        params = h2g.Params(k, s=np.asarray(hc.fr_to_limbs(0x1234567), dtype=np.uint64))
+        pk = h2g.ProvingKey(params, circ)
+        vk = h2g.VerifyingKey.from_pk(pk)
+        proofs = [pk.create_proof(wit, seed=i.to_bytes(32, "little")) for i in range(1, 257)]
+        insts = [[h2g.instance_columns(wit, circ)]] * len(proofs)
+        ts = []
+        for it in range(9):
+            t0 = time.perf_counter()
+            v, st = vk.verify_batch(proofs, insts, rng_seed=bytes([it + 1] * 32))
+            if it >= 2:
+                ts.append((time.perf_counter() - t0, h2g.verify_stages()))
+            assert v == [h2g.VERIFY_OK] * len(proofs) and st[0] == 1
+        ts.sort()
+        out["verify"][spec] = {"median_ms": round(ts[len(ts) // 2][0] * 1e3, 3), "min_ms": round(ts[0][0] * 1e3, 3),
+                               "stages_ms": [round(x, 3) for x in ts[len(ts) // 2][1]], "stats": list(st[:3])}
+        vk.close()
+        pk.close()
+        params.close()
     h2g.shutdown()
     print("AB " + json.dumps(out), flush=True)
 
@@ -91,6 +114,7 @@ def main():
     ap.add_argument("--variants", nargs="+", default=[""])
     ap.add_argument("--msm", default="")
     ap.add_argument("--prove", default="")
+    ap.add_argument("--verify", default="")
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--child", action="store_true")
     args = ap.parse_args()
@@ -104,7 +128,8 @@ def main():
                 k, val = kv.split("=", 1)
                 env[k] = val
             p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--msm", args.msm,
-                                "--prove", args.prove], env=env, capture_output=True, text=True, timeout=600)
+                                "--prove", args.prove, "--verify", args.verify], env=env, capture_output=True,
+                               text=True, timeout=600)
             line = [ln for ln in p.stdout.splitlines() if ln.startswith("AB ")]
             if p.returncode != 0 or not line:
                 print(f"variant {v!r} failed rc={p.returncode}\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}", flush=True)
@@ -116,7 +141,9 @@ def main():
     for v, rs in res.items():
         msm = {ln: [r["msm"][ln]["ms"] for r in rs] for ln in rs[0]["msm"]}
         prove = {k: [r["prove"][k]["median_ms"] for r in rs] for k in rs[0]["prove"]}
-        print(json.dumps({"variant": v or "(default)", "msm_ms": msm, "prove_median_ms": prove}), flush=True)
+        verify = {k: [r["verify"][k]["median_ms"] for r in rs] for k in rs[0].get("verify", {})}
+        print(json.dumps({"variant": v or "(default)", "msm_ms": msm, "prove_median_ms": prove,
+                          "verify_batch_median_ms": verify}), flush=True)
     return 0
 
 

@@ -507,6 +507,8 @@ int h2g_shutdown(void) {
     if (dev->xev_in) (void)hipEventDestroy(dev->xev_in);
     if (dev->xev_done) (void)hipEventDestroy(dev->xev_done);
     dev->xwork.release();
+    dev->pair_tab.release();
+    dev->pair_valid = false;
     if (dev->h_windows) (void)hipHostFree(dev->h_windows);
     (void)hipStreamDestroy(dev->stream);
   }

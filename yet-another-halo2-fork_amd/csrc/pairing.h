@@ -13,6 +13,9 @@
 // the two Frobenius-twisted closing lines, shared squarings over several pairs, then the final
 // exponentiation (p^12 - 1) / r = (p^6 - 1)(p^2 + 1) * (p^4 - p^2 + 1) / r: the easy part by
 // conjugation, inversion and Frobenius, the hard part by plain square-and-multiply.
+// A line splits into what its G2 points decide (LineCoeffs: lam and c = yt - lam xt) and its
+// evaluation at the G1 point; g2_line_table keeps the first part for a fixed G2 point, which
+// is all the device pairing (pairing_dev.hip) needs of G2.
 #pragma once
 #include <utility>
 #include <vector>
@@ -159,10 +162,19 @@ struct PairingPair {
   G1Affine p;
   G2Affine q;
 };
+// what a Miller-loop line keeps of its G2 points: l(xp, yp) = -yp + (lam xp) w + c w^3
+struct LineCoeffs {
+  Fq2 lam, c;
+};
+// 6u + 2 = 2^64 + ATE_LO; a line table has one doubling line per bit of ATE_LO, one addition
+// line per set bit and the two closing lines
+static constexpr uint64_t ATE_LO = 0x9d797039be763ba8ull;
+static constexpr int ATE_LINES = 64 + 36 + 2;
 namespace pairing_detail {
-// the line through the twisted points t and q (the tangent when they are equal) at the G1
-// point (xp, yp), and t <- t + q.  false: a vertical line (points outside the r-torsion)
-inline bool line(G2Affine* t, const G2Affine& q, const Fq& xp, const Fq& yp, Fq12* out) {
+// the line through the twisted points t and q (the tangent when they are equal), the part that
+// the G2 points alone decide: its slope lam and c = yt - lam xt, and t <- t + q.
+// false: a vertical line (points outside the r-torsion)
+inline bool line_coeffs(G2Affine* t, const G2Affine& q, LineCoeffs* out) {
   Fq2 lam;
   if (fq2_eq(t->x, q.x) && fq2_eq(t->y, q.y)) {
     const Fq2 x2 = fq2_sqr(t->x);
@@ -173,14 +185,25 @@ inline bool line(G2Affine* t, const G2Affine& q, const Fq& xp, const Fq& yp, Fq1
   } else {
     lam = fq2_mul(fq2_sub(q.y, t->y), fq2_inv(fq2_sub(q.x, t->x)));
   }
-  for (auto& c : out->c) c = fq2_zero();
-  out->c[0] = {Fq::zero() - yp, Fq::zero()};
-  out->c[1] = fq2_scale(lam, xp);
-  out->c[3] = fq2_sub(t->y, fq2_mul(lam, t->x));
+  out->lam = lam;
+  out->c = fq2_sub(t->y, fq2_mul(lam, t->x));
   const Fq2 x3 = fq2_sub(fq2_sub(fq2_sqr(lam), t->x), q.x);
   const Fq2 y3 = fq2_sub(fq2_mul(lam, fq2_sub(t->x, x3)), t->y);
   t->x = x3;
   t->y = y3;
+  return true;
+}
+// that line at the G1 point (xp, yp): l = -yp + (lam xp) w + c w^3
+inline void line_eval(const LineCoeffs& lc, const Fq& xp, const Fq& yp, Fq12* out) {
+  for (auto& c : out->c) c = fq2_zero();
+  out->c[0] = {Fq::zero() - yp, Fq::zero()};
+  out->c[1] = fq2_scale(lc.lam, xp);
+  out->c[3] = lc.c;
+}
+inline bool line(G2Affine* t, const G2Affine& q, const Fq& xp, const Fq& yp, Fq12* out) {
+  LineCoeffs lc;
+  if (!line_coeffs(t, q, &lc)) return false;
+  line_eval(lc, xp, yp, out);
   return true;
 }
 inline G2Affine frob_twist(const G2Affine& q) {
@@ -192,7 +215,6 @@ inline G2Affine frob_twist(const G2Affine& q) {
 // prod_i f_{6u+2, Q_i}(P_i) with the closing lines; pairs with an identity on either side
 // contribute 1.  false: a vertical line was met (a G2 point outside the r-torsion).
 inline bool miller_loop(const std::vector<PairingPair>& pairs, Fq12* out) {
-  static constexpr uint64_t ATE_LO = 0x9d797039be763ba8ull;  // 6u + 2 = 2^64 + ATE_LO
   std::vector<const PairingPair*> live;
   for (const auto& pr : pairs)
     if (!pr.p.is_identity() && !pr.q.is_identity()) live.push_back(&pr);
@@ -222,6 +244,57 @@ inline bool miller_loop(const std::vector<PairingPair>& pairs, Fq12* out) {
   }
   *out = f;
   return true;
+}
+
+// The lines of miller_loop for one fixed G2 point, in the loop's order: for every bit of
+// ATE_LO from the top the doubling line, then the addition line where the bit is set, then the
+// two Frobenius-twisted closing lines (ATE_LINES in all).  With both G2 arguments of a check
+// fixed, the Miller loop needs no G2 arithmetic: pairing_dev.hip reads these tables.
+// false: a vertical line was met (a G2 point outside the r-torsion), or q is the identity.
+inline bool g2_line_table(const G2Affine& q, std::vector<LineCoeffs>* out) {
+  out->clear();
+  if (q.is_identity()) return false;
+  G2Affine t = q;
+  LineCoeffs lc;
+  for (int i = 63; i >= 0; i--) {
+    if (!pairing_detail::line_coeffs(&t, t, &lc)) return false;
+    out->push_back(lc);
+    if ((ATE_LO >> i) & 1) {
+      if (!pairing_detail::line_coeffs(&t, q, &lc)) return false;
+      out->push_back(lc);
+    }
+  }
+  const G2Affine q1 = pairing_detail::frob_twist(q);
+  G2Affine nq2 = pairing_detail::frob_twist(q1);
+  nq2.y = fq2_neg(nq2.y);
+  if (!pairing_detail::line_coeffs(&t, q1, &lc)) return false;
+  out->push_back(lc);
+  if (!pairing_detail::line_coeffs(&t, nq2, &lc)) return false;
+  out->push_back(lc);
+  return true;
+}
+
+// f_{6u+2, Q}(P) with the closing lines from Q's line table: the value miller_loop gives for
+// the one pair (P, Q), and the order of operations the device kernel follows; 1 when P is the
+// identity
+inline Fq12 miller_from_lines(const std::vector<LineCoeffs>& tab, const G1Affine& p) {
+  Fq12 f = fq12_one(), ln;
+  if (p.is_identity() || tab.size() != (size_t)ATE_LINES) return f;
+  size_t k = 0;
+  for (int i = 63; i >= 0; i--) {
+    f = fq12_sqr(f);
+    pairing_detail::line_eval(tab[k++], p.x, p.y, &ln);
+    f = fq12_mul(f, ln);
+    if ((ATE_LO >> i) & 1) {
+      pairing_detail::line_eval(tab[k++], p.x, p.y, &ln);
+      f = fq12_mul(f, ln);
+    }
+  }
+  for (int j = 0; j < 2; j++) {
+    pairing_detail::line_eval(tab[k++], p.x, p.y, &ln);
+    f = fq12_mul(f, ln);
+  }
+  return f;
 }
 
 inline Fq12 final_exponentiation(const Fq12& f) {

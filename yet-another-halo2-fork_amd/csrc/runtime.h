@@ -177,6 +177,11 @@ struct Device {
   hipStream_t xstream = nullptr;
   DevBuf xwork;
   hipEvent_t xev_in = nullptr, xev_done = nullptr;
+  // the device pairing's line tables (pairing_dev.h PairingTable) of the verifier params last
+  // used, keyed by the 32 words of (g2, s_g2); rebuilt on the host when the key changes
+  DevBuf pair_tab;
+  uint64_t pair_key[32] = {};
+  bool pair_valid = false;
 };
 
 extern std::vector<std::unique_ptr<Device>> g_devs;

@@ -10,6 +10,8 @@
 //                                    with h2g_multiopen_verify below
 //   l_i_range                        poly/domain.rs:425-450
 //   DualMSM::check                   poly/kzg/msm.rs:188-206
+// The device pairing (pairing_dev.hip) serves h2g_pairing_check_batch and, when
+// h2g_verify_set_isolation(1) is set, gives a failing batch's proofs their verdicts in one launch.
 // (oracle/py/verifier.py restates the same sources in Python and is what the tests compare
 // verdicts with).
 //
@@ -25,6 +27,7 @@
 #include "msm_seg.h"
 #include "multiopen.h"
 #include "pairing.h"
+#include "pairing_dev.h"
 
 using namespace h2g;
 using namespace h2g::rt;
@@ -40,6 +43,7 @@ namespace {
 constexpr uint32_t KEY_H = 0xFFFFFFFFu;  // the query key of the h(X) MSM (no single base)
 
 double g_verify_ms[4] = {0, 0, 0, 0};  // host, decompression, MSM, pairing of the last call
+int g_isolation = 0;                   // h2g_verify_set_isolation
 
 double now_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -510,6 +514,63 @@ bool dual_check(const VerifierPoints& vp, const G1Affine& l, const G1Affine& r) 
   return pairing_check(pairs);
 }
 
+// The device pairing's tables for these params: built on the host and uploaded when (g2, s_g2)
+// differ from the last call's.  The device state owns them (runtime.h Device::pair_tab).
+int pairing_tables(Device* d, const VerifierPoints& vp, const PairingTable** out) {
+  uint64_t key[32];
+  std::memcpy(key, &vp.g2, sizeof(G2Affine));
+  std::memcpy(key + 16, &vp.s_g2, sizeof(G2Affine));
+  if (!d->pair_valid || std::memcmp(key, d->pair_key, sizeof(key)) != 0) {
+    auto tab = std::make_unique<PairingTable>();
+    if (!pairing_table_build(vp.g2, vp.s_g2, tab.get()))
+      return fail(H2G_ERR_ARG, "pairing: a G2 point of the verifier params is outside the r-torsion");
+    d->pair_valid = false;
+    HIPCHK(d->pair_tab.ensure(sizeof(PairingTable)));
+    HIPCHK(hipDeviceSynchronize());  // a launch on a caller's stream may still read the old table
+    HIPCHK(hipMemcpy(d->pair_tab.p, tab.get(), sizeof(PairingTable), hipMemcpyHostToDevice));
+    std::memcpy(d->pair_key, key, sizeof(key));
+    d->pair_valid = true;
+  }
+  *out = d->pair_tab.as<const PairingTable>();
+  return H2G_OK;
+}
+
+// h2g_pairing_check_batch and h2g_debug_pairing_values: validate, copy in, one launch, copy out
+int pairing_host_impl(Device* d, const h2g_verifier_params* vpp, const uint64_t* lr, size_t count, int32_t* ok,
+                      uint64_t* miller, uint64_t* gt) {
+  VerifierPoints vp;
+  RCCHK(load_vp(vpp, &vp));
+  if (count == 0) return H2G_OK;
+  if (!lr) return fail(H2G_ERR_ARG, "pairing_check: null argument");
+  if (count > (1u << 24)) return fail(H2G_ERR_ARG, "pairing_check: too many checks");
+  const Fq three = from_u64<FqParams>(3);
+  for (size_t i = 0; i < 2 * count; i++) {
+    G1Affine c;
+    std::memcpy(&c, lr + 8 * i, sizeof(G1Affine));
+    if (!fq_below_m(c.x) || !fq_below_m(c.y) || (!c.is_identity() && sqr(c.y) != sqr(c.x) * c.x + three))
+      return fail(H2G_ERR_ARG, std::string("pairing_check: the ") + (i & 1 ? "right" : "left") + " point of check " +
+                                   std::to_string(i / 2) + " is not a point of the curve");
+  }
+  const PairingTable* tab = nullptr;
+  RCCHK(pairing_tables(d, vp, &tab));
+  hipStream_t st = d->stream;
+  DevMem d_lr, d_ok, d_ml, d_gt;
+  StreamSyncGuard guard{st};
+  HIPCHK(hipMalloc(&d_lr.p, 2 * count * sizeof(G1Affine)));
+  HIPCHK(hipMalloc(&d_ok.p, count * 4));
+  if (miller) HIPCHK(hipMalloc(&d_ml.p, count * 6 * sizeof(Fq2)));
+  if (gt) HIPCHK(hipMalloc(&d_gt.p, count * 6 * sizeof(Fq2)));
+  std::vector<int32_t> okv(count);
+  HIPCHK(hipMemcpyAsync(d_lr.p, lr, 2 * count * sizeof(G1Affine), hipMemcpyHostToDevice, st));
+  HIPCHK(pairing_check_launch(tab, (const G1Affine*)d_lr.p, count, (int32_t*)d_ok.p, (Fq2*)d_ml.p, (Fq2*)d_gt.p, st));
+  HIPCHK(hipMemcpyAsync(okv.data(), d_ok.p, count * 4, hipMemcpyDeviceToHost, st));
+  if (miller) HIPCHK(hipMemcpyAsync(miller, d_ml.p, count * 6 * sizeof(Fq2), hipMemcpyDeviceToHost, st));
+  if (gt) HIPCHK(hipMemcpyAsync(gt, d_gt.p, count * 6 * sizeof(Fq2), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (ok) std::memcpy(ok, okv.data(), count * 4);
+  return H2G_OK;
+}
+
 int verify_impl(Device* d, uint64_t vk_h, const h2g_verifier_params* vpp, int multiopen, int transcript,
                 const h2g_verify_item* items, size_t count, const h2g_rng* rng, bool combine, int32_t* verdicts,
                 uint64_t stats[4]) {
@@ -702,8 +763,25 @@ int verify_impl(Device* d, uint64_t vk_h, const h2g_verifier_params* vpp, int mu
       if (test(mid, hi)) mark(mid, hi, H2G_VERIFY_OK);
       else if (!rc) resolve(mid, hi);
     };
-    if (test(0, W)) mark(0, W, H2G_VERIFY_OK);
-    else if (!rc) resolve(0, W);
+    if (test(0, W)) {
+      mark(0, W, H2G_VERIFY_OK);
+    } else if (!rc && g_isolation == 1) {
+      // one launch over the resident (L_i, R_i): each proof's own check, no random factor
+      const double ta = now_ms();
+      const PairingTable* tab = nullptr;
+      RCCHK(pairing_tables(d, vp, &tab));
+      DevMem d_ok;
+      std::vector<int32_t> okv(W);
+      HIPCHK(hipMalloc(&d_ok.p, W * 4));
+      HIPCHK(pairing_check_launch(tab, (const G1Affine*)d_lr.p, W, (int32_t*)d_ok.p, nullptr, nullptr, st));
+      HIPCHK(hipMemcpyAsync(okv.data(), d_ok.p, W * 4, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      for (size_t j = 0; j < W; j++) verdicts[well[j]] = okv[j] ? H2G_VERIFY_OK : H2G_VERIFY_REJECTED;
+      t_pair += now_ms() - ta;
+      n_checks += W;
+    } else if (!rc) {
+      resolve(0, W);
+    }
     if (rc) return rc;
   }
   if (stats) {
@@ -856,6 +934,41 @@ int h2g_multiopen_verify(const h2g_verifier_params* vpp, int scheme, uint64_t tr
   if (lr) std::memcpy(lr, out, sizeof(out));
   *verdict = dual_check(vp, out[0], out[1]) ? H2G_VERIFY_OK : H2G_VERIFY_REJECTED;
   return H2G_OK;
+}
+
+int h2g_pairing_check_batch(const h2g_verifier_params* vp, const uint64_t* lr, size_t count, int32_t* ok) {
+  NEED_DEV_P();
+  if (count && !ok) return fail(H2G_ERR_ARG, "pairing_check: null argument");
+  return pairing_host_impl(d, vp, lr, count, ok, nullptr, nullptr);
+}
+
+int h2g_pairing_check_batch_dev(const h2g_verifier_params* vpp, const void* d_lr, size_t count, void* d_ok,
+                                void* stream) {
+  NEED_DEV_P();
+  VerifierPoints vp;
+  RCCHK(load_vp(vpp, &vp));
+  if (count == 0) return H2G_OK;
+  if (!d_lr || !d_ok) return fail(H2G_ERR_ARG, "pairing_check_dev: null argument");
+  if (((uintptr_t)d_lr | (uintptr_t)d_ok) & 15) return fail(H2G_ERR_ARG, "pairing_check_dev: misaligned pointer");
+  if (count > (1u << 24)) return fail(H2G_ERR_ARG, "pairing_check_dev: too many checks");
+  const PairingTable* tab = nullptr;
+  RCCHK(pairing_tables(d, vp, &tab));
+  HIPCHK(pairing_check_launch(tab, (const G1Affine*)d_lr, count, (int32_t*)d_ok, nullptr, nullptr,
+                              pick_stream(d, stream)));
+  return H2G_OK;
+}
+
+int h2g_verify_set_isolation(int mode) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  if (mode != 0 && mode != 1) return fail(H2G_ERR_ARG, "verify_set_isolation: mode must be 0 (bisection) or 1 (device checks)");
+  g_isolation = mode;
+  return H2G_OK;
+}
+
+int h2g_debug_pairing_values(const h2g_verifier_params* vp, const uint64_t* lr, size_t count, uint64_t* miller,
+                             uint64_t* gt) {
+  NEED_DEV_P();
+  return pairing_host_impl(d, vp, lr, count, nullptr, miller, gt);
 }
 
 /* wall milliseconds of the last h2g_verify_proof / h2g_verify_batch: [0] host (transcripts,

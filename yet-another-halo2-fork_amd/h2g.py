@@ -173,6 +173,10 @@ _SIGS = {
     "h2g_kate_division_dev": ([VP, SZ, U64P, VP, VP], I32),
     "h2g_multiopen_prove": ([U64, I32, U64, VP, SZ, VP, SZ], I32),
     "h2g_multiopen_verify": ([VP, I32, U64, U64P, SZ, VP, SZ, ctypes.POINTER(ctypes.c_int32), U64P], I32),
+    "h2g_pairing_check_batch": ([VP, U64P, SZ, ctypes.POINTER(ctypes.c_int32)], I32),
+    "h2g_pairing_check_batch_dev": ([VP, VP, SZ, VP, VP], I32),
+    "h2g_verify_set_isolation": ([I32], I32),
+    "h2g_debug_pairing_values": ([VP, U64P, SZ, U64P, U64P], I32),
 }
 
 TRANSCRIPTS = {"blake2b": 0, "keccak256": 1}  # Blake2bWrite / Keccak256Write (h2g_pk_set_transcript)
@@ -1287,6 +1291,40 @@ def multiopen_verify(vp, transcript, commitments, queries, scheme="shplonk"):
                                      p64(cm) if cm.size else None, len(cm), qs, len(queries),
                                      ctypes.byref(verdict), p64(lr)))
     return verdict.value, (lr if verdict.value != VERIFY_MALFORMED else None)
+
+
+def pairing_check_batch(vp, lr, dev_count=None, d_ok=None, stream=None):
+    """h2g_pairing_check_batch: lr (count, 2, 8) affine (left, right) pairs, the layout
+    multiopen_verify returns -> (count,) int32, 1 where e(left, s_g2) == e(right, g2), all in one
+    device launch.  With dev_count, lr and d_ok are device pointers (h2g_pairing_check_batch_dev:
+    asynchronous on `stream`, points not validated) and nothing is returned."""
+    if dev_count is not None:
+        check(lib().h2g_pairing_check_batch_dev(ctypes.byref(vp), VP(lr), dev_count, VP(d_ok),
+                                                VP(stream) if stream else None))
+        return None
+    a = np.ascontiguousarray(lr, dtype=np.uint64).reshape(-1, 16)
+    ok = np.zeros(len(a), dtype=np.int32)
+    check(lib().h2g_pairing_check_batch(ctypes.byref(vp), p64(a) if a.size else None, len(a),
+                                        ok.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+    return ok
+
+
+def verify_set_isolation(mode):
+    """h2g_verify_set_isolation: how verify_batch resolves a failing batch, 0 bisection
+    (default), 1 one device launch of per-proof pairing checks.  Process-wide."""
+    check(lib().h2g_verify_set_isolation(mode))
+
+
+def debug_pairing_values(vp, lr, miller=True, gt=True):
+    """h2g_debug_pairing_values (test seam) -> (miller, gt), each (count, 6, 2, 4) u64 Montgomery
+    limbs (Fq2 coefficients of 1, w, .., w^5) or None"""
+    a = np.ascontiguousarray(lr, dtype=np.uint64).reshape(-1, 16)
+    m = np.zeros((len(a), 6, 2, 4), dtype=np.uint64) if miller else None
+    g = np.zeros((len(a), 6, 2, 4), dtype=np.uint64) if gt else None
+    check(lib().h2g_debug_pairing_values(ctypes.byref(vp), p64(a) if a.size else None, len(a),
+                                         p64(m) if m is not None and m.size else None,
+                                         p64(g) if g is not None and g.size else None))
+    return m, g
 
 
 def fr_eval(poly, x, dev_len=None, stream=None):
