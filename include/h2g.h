@@ -128,6 +128,20 @@ int h2g_lagrange_to_coeff_dev(uint64_t dom, void* d_a, void* stream);
 /* coeff_to_extended (domain.rs:230-244): in n, out 2^extended_k */
 int h2g_coeff_to_extended(uint64_t dom, const uint64_t* a, uint64_t* out);
 int h2g_coeff_to_extended_dev(uint64_t dom, const void* d_a, void* d_out, void* stream);
+/* Sub-coset t of coeff_to_extended, for `count` polynomials at once: outs[i][m] =
+ * coeff_to_extended(polys[i])[t + 2^(extended_k - k) m], m < n -- the evaluations on
+ * zeta w_ext^t <omega>, by one n-point transform per polynomial (the twist w_ext^(t j) is
+ * formed inside it; no extended array exists).  A quotient loop that walks the extended
+ * domain sub-coset by sub-coset needs n-point slots only.  t < 2^(extended_k - k); polys /
+ * outs are host arrays of `count` pointers to n elements; no outs[i] may overlap a polys[j]
+ * (H2G_ERR_ARG).  Any count: NTT_MAX_BATCH (8) transforms share a launch. */
+int h2g_coeff_to_subcoset(uint64_t dom, const uint64_t* const* polys, int count, uint64_t t, uint64_t* const* outs);
+int h2g_coeff_to_subcoset_dev(uint64_t dom, const void* const* d_polys, int count, uint64_t t, void* const* d_outs,
+                              void* stream);
+/* The same results by the composition the fused transform replaces -- a twist launch per
+ * column, then the batched NTT -- for measurements and cross-checks (tools/streamed_bench.py). */
+int h2g_debug_coeff_to_subcoset_unfused_dev(uint64_t dom, const void* const* d_polys, int count, uint64_t t,
+                                            void* const* d_outs, void* stream);
 /* extended_to_coeff (domain.rs:271-293): in 2^extended_k, out n*(j-1) (truncated) */
 int h2g_extended_to_coeff(uint64_t dom, const uint64_t* a, uint64_t* out);
 int h2g_extended_to_coeff_dev(uint64_t dom, const void* d_a, void* d_out, void* stream);
@@ -295,6 +309,33 @@ int h2g_pk_free(uint64_t pk);
 int h2g_pk_write(uint64_t pk, int format, uint8_t* out, size_t cap, size_t* len);
 int h2g_pk_read(uint64_t params, const h2g_circuit* circuit, const uint8_t* buf, size_t len, int format,
                 uint64_t* pk);
+/* Key options.  `cosets` says how a key holds the columns that the quotient evaluation
+ * (evaluate_h) reads on the extended domain:
+ *   H2G_COSETS_RESIDENT  every such column as its extended coset, 2^extended_k elements:
+ *                        the key's fixed / permutation / l_0, l_last, l_active cosets and,
+ *                        per circuit of a proof, one per advice and instance column, one per
+ *                        permutation set, three per lookup and one per shuffle.
+ *   H2G_COSETS_STREAMED  one n-element slot per such column.  create_proof evaluates h(X)
+ *                        one sub-coset of the extended domain at a time and refills the
+ *                        slots from the coefficient forms for each (h2g_coeff_to_subcoset's
+ *                        transform); only h(X)'s own three buffers stay extended.  Proofs,
+ *                        key bytes (h2g_pk_write), verifying key and witness checks are the
+ *                        same bytes as a resident key's; the price is the key's fixed /
+ *                        permutation / l transforms redone in every proof.  Not combined
+ *                        with an SPMD transport of more than one rank (H2G_ERR_STATE).
+ * `size` is sizeof(h2g_key_options).  NULL options or mode 0 are h2g_keygen / h2g_pk_read
+ * exactly; an unknown mode is H2G_ERR_ARG.  h2g_pk_read_opts in streamed mode accepts and
+ * refuses the same files: the file's cosets pass the format's checks in scratch and are
+ * dropped. */
+enum { H2G_COSETS_RESIDENT = 0, H2G_COSETS_STREAMED = 1 };
+typedef struct { uint32_t size; uint32_t cosets; } h2g_key_options;
+int h2g_keygen_opts(uint64_t params, const h2g_circuit* circuit, const h2g_key_options* opts, uint64_t* pk);
+int h2g_pk_read_opts(uint64_t params, const h2g_circuit* circuit, const uint8_t* buf, size_t len, int format,
+                     const h2g_key_options* opts, uint64_t* pk);
+/* out[0] the coset mode; out[1] the device bytes the key holds now (its arrays and the
+ * per-proof workspace grown so far); out[2] those of them in arrays of 2^extended_k
+ * elements; out[3] 0. */
+int h2g_pk_memory(uint64_t pk, uint64_t out[4]);
 /* degree, blinding_factors, extended_k, #perm sets, #advice/#fixed/#instance queries */
 int h2g_pk_info(uint64_t pk, int32_t info[8]);
 /* Diagnostics (read only): the value width in bits that the next proof's sort will assume

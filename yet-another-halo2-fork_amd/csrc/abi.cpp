@@ -25,6 +25,7 @@
 #include "msm.h"
 #include "ntt.h"
 #include "poly.h"
+#include "prover_kernels.h"
 #include "srs.h"
 
 using namespace h2g;
@@ -397,6 +398,53 @@ int coeff_to_extended_batch(Device* d, const Domain& dm, const Fr* const* src, F
   return H2G_OK;
 }
 
+// Sub-coset t of the extended coset of each polynomial: dst[c][m] = coeff_to_extended(src[c])[t +
+// 2^e m], e = ek - k.  Row t + 2^e m is the point zeta w_ext^t w^m, so this is the n-point
+// NTT of src_j zeta^(j mod 3) w_ext^(t j); the factors are formed inside the transform's
+// first pass (ntt.h in_twist) from the two-level powers of w_ext^-1 that extended_to_coeff's
+// tables hold anyway: w_ext^t = (w_ext^-1)^(2^ek - t).
+int coeff_to_subcoset_batch(Device* d, const Domain& dm, const Fr* const* src, Fr* const* dst, int count, uint64_t t,
+                            hipStream_t st) {
+  const uint64_t n = 1ull << dm.k, ext = 1ull << dm.ek;
+  if (t >= (ext >> dm.k)) return fail(H2G_ERR_ARG, "coeff_to_subcoset: t past the last sub-coset");
+  const int L = (int)dm.k;
+  NttTables pw;  // extended_to_coeff's tables (same key: the scale it folds)
+  RCCHK(get_tables(d, dm.ext_omega_inv, (int)dm.ek, st, &pw, dm.ek > NTT_SMALL_MAX_LOG ? dm.ext_ifft_div : Fr::one()));
+  NttArgs a;
+  RCCHK(get_tables(d, dm.omega, L, st, &a.tab));
+  DevBuf& wb = d->xstream != nullptr && st == d->xstream ? d->xwork : d->work;
+  a.n_in = n;
+  a.out_len = n;
+  a.in_distribute = 1;
+  a.in_z1 = dm.g_coset;
+  a.in_z2 = dm.g_coset_inv;
+  a.scale = a.out_z1 = a.out_z2 = Fr::one();
+  a.in_twist = 1;
+  a.tw_g = pow_u64(dm.ext_omega, t);
+  a.tw_lo = pw.lo;
+  a.tw_hi = pw.hi;
+  a.tw_bits = pw.b;
+  a.tw_mask = ext - 1;
+  a.tw_mul = (ext - t) & a.tw_mask;
+  for (int b0 = 0; b0 < count; b0 += NTT_MAX_BATCH) {
+    const int B = std::min(NTT_MAX_BATCH, count - b0);
+    if (L > NTT_SMALL_MAX_LOG) {
+      hipError_t e = wb.ensure((size_t)B * n * sizeof(Fr));
+      if (e != hipSuccess) return hip_fail(e, "ntt work buffer");
+    }
+    a.work = reinterpret_cast<Fr*>(wb.p);
+    a.count = B;
+    a.src = src[b0];
+    a.dst = dst[b0];
+    for (int b = 0; b < B; b++) {
+      a.srcs[b] = src[b0 + b];
+      a.dsts[b] = dst[b0 + b];
+    }
+    HIPCHK(ntt_run(a, st));
+  }
+  return H2G_OK;
+}
+
 // extended_to_coeff (domain.rs:271-293): inverse FFT, * 1/2^ek, undistribute, truncate to n (j - 1)
 int extended_to_coeff(Device* d, const Domain& dm, const Fr* src, Fr* dst, hipStream_t st) {
   const Fr one = Fr::one();
@@ -746,6 +794,50 @@ int h2g_coeff_to_extended_dev(uint64_t dom, const void* a, void* out, void* stre
   return coeff_to_extended(d, *dm, (const Fr*)a, (Fr*)out, pick_stream(d, stream));
 }
 
+int h2g_coeff_to_subcoset_dev(uint64_t dom, const void* const* polys, int count, uint64_t t, void* const* outs,
+                              void* stream) {
+  NEED_DEV();
+  Domain* dm = get_dom(dom);
+  if (!dm) return fail(H2G_ERR_HANDLE, "unknown domain");
+  if (count < 0 || (count && (!polys || !outs))) return fail(H2G_ERR_ARG, "coeff_to_subcoset: null");
+  if (t >> (dm->ek - dm->k)) return fail(H2G_ERR_ARG, "coeff_to_subcoset: t past the last sub-coset");
+  // a slot is written while other polynomials of its batch are still read
+  const size_t bytes = sizeof(Fr) << dm->k;
+  for (int i = 0; i < count; i++) {
+    if (!polys[i] || !outs[i]) return fail(H2G_ERR_ARG, "coeff_to_subcoset: null");
+    for (int j = 0; j < count; j++) {
+      const char *o = (const char*)outs[i], *p = (const char*)polys[j], *o2 = (const char*)outs[j];
+      if (o < p + bytes && p < o + bytes) return fail(H2G_ERR_ARG, "coeff_to_subcoset: in and out must differ");
+      if (i != j && o < o2 + bytes && o2 < o + bytes) return fail(H2G_ERR_ARG, "coeff_to_subcoset: outs overlap");
+    }
+  }
+  return coeff_to_subcoset_batch(d, *dm, (const Fr* const*)polys, (Fr* const*)outs, count, t, pick_stream(d, stream));
+}
+
+// The composition h2g_coeff_to_subcoset_dev replaces, for measurements and cross-checks: one
+// twist launch per column (a read and a write of n elements each; the SPMD sub-coset split's
+// subcoset_twist) ahead of the batched NTT with the zeta distribution.  Same results.
+int h2g_debug_coeff_to_subcoset_unfused_dev(uint64_t dom, const void* const* polys, int count, uint64_t t,
+                                            void* const* outs, void* stream) {
+  NEED_DEV();
+  Domain* dm = get_dom(dom);
+  if (!dm) return fail(H2G_ERR_HANDLE, "unknown domain");
+  if (count < 0 || (count && (!polys || !outs))) return fail(H2G_ERR_ARG, "coeff_to_subcoset: null");
+  if (t >> (dm->ek - dm->k)) return fail(H2G_ERR_ARG, "coeff_to_subcoset: t past the last sub-coset");
+  hipStream_t st = pick_stream(d, stream);
+  const uint64_t n = 1ull << dm->k, ext = 1ull << dm->ek;
+  NttTables pw;  // powers of w_ext^-1: w_ext^(t j) = (w_ext^-1)^((2^ek - t) j)
+  RCCHK(get_tables(d, dm->ext_omega_inv, (int)dm->ek, st, &pw, dm->ek > NTT_SMALL_MAX_LOG ? dm->ext_ifft_div : Fr::one()));
+  const PowTable eo{pw.lo, pw.hi, pw.b};
+  const Fr one = Fr::one();
+  for (int i = 0; i < count; i++)
+    HIPCHK(subcoset_twist((const Fr*)polys[i], (Fr*)outs[i], n, eo, (ext - t) & (ext - 1), ext - 1, st));
+  for (int b0 = 0; b0 < count; b0 += NTT_MAX_BATCH)
+    RCCHK(ntt_dev_impl_batch(d, (const Fr* const*)outs + b0, n, (Fr* const*)outs + b0, std::min(NTT_MAX_BATCH, count - b0),
+                             n, (int)dm->k, dm->omega, 1, dm->g_coset, dm->g_coset_inv, 0, one, 0, one, one, st));
+  return H2G_OK;
+}
+
 int h2g_extended_to_coeff_dev(uint64_t dom, const void* a, void* out, void* stream) {
   NEED_DEV();
   Domain* dm = get_dom(dom);
@@ -777,6 +869,40 @@ int h2g_coeff_to_extended(uint64_t dom, const uint64_t* a, uint64_t* out) {
   if (!dm) return fail(H2G_ERR_HANDLE, "unknown domain");
   return host_roundtrip(1ull << dm->k, a, 1ull << dm->ek, out, false,
                         [&](void* da, void* dout) { return h2g_coeff_to_extended_dev(dom, da, dout, nullptr); });
+}
+
+int h2g_coeff_to_subcoset(uint64_t dom, const uint64_t* const* polys, int count, uint64_t t, uint64_t* const* outs) {
+  NEED_DEV();
+  Domain* dm = get_dom(dom);
+  if (!dm) return fail(H2G_ERR_HANDLE, "unknown domain");
+  if (count < 0 || (count && (!polys || !outs))) return fail(H2G_ERR_ARG, "coeff_to_subcoset: null");
+  if (t >> (dm->ek - dm->k)) return fail(H2G_ERR_ARG, "coeff_to_subcoset: t past the last sub-coset");
+  const size_t bytes = sizeof(Fr) << dm->k;
+  for (int i = 0; i < count; i++) {
+    if (!polys[i] || !outs[i]) return fail(H2G_ERR_ARG, "coeff_to_subcoset: null");
+    for (int j = 0; j < count; j++) {
+      const char *o = (const char*)outs[i], *p = (const char*)polys[j];
+      if (o < p + bytes && p < o + bytes) return fail(H2G_ERR_ARG, "coeff_to_subcoset: in and out must differ");
+    }
+  }
+  // NTT_MAX_BATCH polynomials at a time through the device's staging buffers
+  for (int b0 = 0; b0 < count; b0 += NTT_MAX_BATCH) {
+    const int B = std::min(NTT_MAX_BATCH, count - b0);
+    HIPCHK(d->b.ensure((size_t)B * bytes));
+    HIPCHK(d->c.ensure((size_t)B * bytes));
+    const void* in[NTT_MAX_BATCH];
+    void* out[NTT_MAX_BATCH];
+    for (int b = 0; b < B; b++) {
+      in[b] = d->b.p + (size_t)b * bytes;
+      out[b] = d->c.p + (size_t)b * bytes;
+      HIPCHK(hipMemcpyAsync(d->b.p + (size_t)b * bytes, polys[b0 + b], bytes, hipMemcpyHostToDevice, d->stream));
+    }
+    RCCHK(h2g_coeff_to_subcoset_dev(dom, in, B, t, out, nullptr));
+    for (int b = 0; b < B; b++)
+      HIPCHK(hipMemcpyAsync(outs[b0 + b], out[b], bytes, hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+  }
+  return H2G_OK;
 }
 
 int h2g_extended_to_coeff(uint64_t dom, const uint64_t* a, uint64_t* out) {

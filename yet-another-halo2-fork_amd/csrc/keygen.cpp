@@ -235,7 +235,8 @@ std::map<uint64_t, std::unique_ptr<ProvingKey>> g_pks;
 // one more circuit workspace (create_proof over pk.cws.size() + 1 circuits)
 int circuit_ws_add(ProvingKey& pk) {
   auto w = std::make_unique<CircuitWs>();
-  const size_t n = pk.n, ext = pk.ext;
+  const size_t n = pk.n;
+  const size_t ext = pk.cosets ? pk.n : pk.ext;  // streamed: a coset array is one sub-coset slot
   auto vec_alloc = [&](std::vector<Fr*>& v, int cnt, size_t len) -> hipError_t {
     v.assign(cnt, nullptr);
     for (int i = 0; i < cnt; i++) {
@@ -298,6 +299,17 @@ int circuit_ws_add(ProvingKey& pk) {
   HIPCHK(hipMemcpy(w->d_z, zt.data(), zt.size() * sizeof(Fr*), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(w->d_perm_v, pv.data(), pv.size() * sizeof(Fr*), hipMemcpyHostToDevice));
   pk.cws.push_back(std::move(w));
+  return H2G_OK;
+}
+
+// the coset mode of a key-options struct (NULL: resident)
+int key_options_mode(const h2g_key_options* opts, const char* who, int* mode) {
+  *mode = H2G_COSETS_RESIDENT;
+  if (!opts) return H2G_OK;
+  if (opts->size < sizeof(h2g_key_options)) return fail(H2G_ERR_ARG, std::string(who) + ": key options: bad size");
+  if (opts->cosets != H2G_COSETS_RESIDENT && opts->cosets != H2G_COSETS_STREAMED)
+    return fail(H2G_ERR_ARG, std::string(who) + ": key options: unknown coset mode");
+  *mode = (int)opts->cosets;
   return H2G_OK;
 }
 
@@ -487,56 +499,79 @@ int keygen_impl(Device* d, Params& prm, const h2g_circuit* c, ProvingKey& pk, co
     pk.lk_hb.assign(pk.cs.NL, 64);
   }
 
+  // a streamed key holds one sub-coset slot where a resident key holds a coset; a coset
+  // that comes with a key image is checked like the resident key's, in scratch, and dropped
+  const bool streamed = pk.cosets != 0;
+  const size_t clen = streamed ? n : ext;
+  auto image_coset = [&](Fr* resident, const uint8_t* src) -> int {
+    Fr* dst = streamed ? pk.h_ext : resident;
+    HIPCHK(img->upload(dst, src, ext, st));
+    if (streamed && img->bad_raw) HIPCHK(fr_count_unreduced(dst, ext, img->bad_raw, st));
+    return H2G_OK;
+  };
+  if (streamed) HIPCHK(falloc(&pk.h_gather, ext));
   // fixed columns
   HIPCHK(vec_alloc(pk.fixed_lag, pk.cs.F, n));
   HIPCHK(vec_alloc(pk.fixed_poly, pk.cs.F, n));
-  HIPCHK(vec_alloc(pk.fixed_coset, pk.cs.F, ext));
+  HIPCHK(vec_alloc(pk.fixed_coset, pk.cs.F, clen));
   for (int i = 0; i < pk.cs.F; i++) {
     if (img) {
       HIPCHK(img->upload(pk.fixed_lag[i], img->fixed_lag[i], n, st));
       HIPCHK(img->upload(pk.fixed_poly[i], img->fixed_poly[i], n, st));
-      HIPCHK(img->upload(pk.fixed_coset[i], img->fixed_coset[i], ext, st));
+      RCCHK(image_coset(pk.fixed_coset[i], img->fixed_coset[i]));
       continue;
     }
     HIPCHK(hipMemcpyAsync(pk.fixed_lag[i], c->fixed_values + 4 * n * i, n * sizeof(Fr), hipMemcpyHostToDevice, st));
     RCCHK(lagrange_to_coeff(d, pk.dom, pk.fixed_lag[i], pk.fixed_poly[i], st));
-    RCCHK(coeff_to_extended(d, pk.dom, pk.fixed_poly[i], pk.fixed_coset[i], st));
+    if (!streamed) RCCHK(coeff_to_extended(d, pk.dom, pk.fixed_poly[i], pk.fixed_coset[i], st));
   }
   // l_0, l_last, l_active (keygen.rs:147-175)
-  HIPCHK(falloc(&pk.l0, ext));
-  HIPCHK(falloc(&pk.l_last, ext));
-  HIPCHK(falloc(&pk.l_active, ext));
+  HIPCHK(falloc(&pk.l0, clen));
+  HIPCHK(falloc(&pk.l_last, clen));
+  HIPCHK(falloc(&pk.l_active, clen));
   if (img) {
-    HIPCHK(img->upload(pk.l0, img->l0, ext, st));
-    HIPCHK(img->upload(pk.l_last, img->l_last, ext, st));
-    HIPCHK(img->upload(pk.l_active, img->l_active, ext, st));
-  } else {
+    RCCHK(image_coset(pk.l0, img->l0));
+    RCCHK(image_coset(pk.l_last, img->l_last));
+    RCCHK(image_coset(pk.l_active, img->l_active));
+  }
+  if (!img || streamed) {
     const Fr one = Fr::one();
     std::vector<Fr> ones(pk.cs.bf, one);
-    auto lagrange_unit = [&](size_t row0, int count, Fr* out) -> int {
+    // the Lagrange polynomial(s) of `count` rows from row0: coefficient form, and (resident)
+    // its extended coset
+    auto lagrange_unit = [&](size_t row0, int count, Fr* poly, Fr* out) -> int {
       HIPCHK(hipMemsetAsync(pk.pre, 0, n * sizeof(Fr), st));
       HIPCHK(hipMemcpyAsync(pk.pre + row0, ones.data(), count * sizeof(Fr), hipMemcpyHostToDevice, st));
-      RCCHK(lagrange_to_coeff(d, pk.dom, pk.pre, pk.mod, st));
-      RCCHK(coeff_to_extended(d, pk.dom, pk.mod, out, st));
+      RCCHK(lagrange_to_coeff(d, pk.dom, pk.pre, poly, st));
+      if (out) RCCHK(coeff_to_extended(d, pk.dom, poly, out, st));
       HIPCHK(hipStreamSynchronize(st));
       return H2G_OK;
     };
-    RCCHK(lagrange_unit(0, 1, pk.l0));
-    RCCHK(lagrange_unit(n - pk.cs.bf, pk.cs.bf, pk.h_ext));  // l_blind
-    RCCHK(lagrange_unit(n - pk.cs.bf - 1, 1, pk.l_last));
-    HIPCHK(poly_binop(POLY_ADD, pk.l_last, pk.h_ext, one, pk.l_active, ext, st));
-    HIPCHK(poly_binop(POLY_SUB_CONST, pk.l_active, nullptr, one, pk.l_active, ext, st));
-    HIPCHK(poly_binop(POLY_SCALE, pk.l_active, nullptr, fr_neg_one(), pk.l_active, ext, st));
+    if (streamed) {
+      HIPCHK(falloc(&pk.l0_poly, n));
+      HIPCHK(falloc(&pk.l_last_poly, n));
+      HIPCHK(falloc(&pk.l_blind_poly, n));
+      RCCHK(lagrange_unit(0, 1, pk.l0_poly, nullptr));
+      RCCHK(lagrange_unit(n - pk.cs.bf, pk.cs.bf, pk.l_blind_poly, nullptr));
+      RCCHK(lagrange_unit(n - pk.cs.bf - 1, 1, pk.l_last_poly, nullptr));
+    } else {
+      RCCHK(lagrange_unit(0, 1, pk.mod, pk.l0));
+      RCCHK(lagrange_unit(n - pk.cs.bf, pk.cs.bf, pk.mod, pk.h_ext));  // l_blind
+      RCCHK(lagrange_unit(n - pk.cs.bf - 1, 1, pk.mod, pk.l_last));
+      HIPCHK(poly_binop(POLY_ADD, pk.l_last, pk.h_ext, one, pk.l_active, ext, st));
+      HIPCHK(poly_binop(POLY_SUB_CONST, pk.l_active, nullptr, one, pk.l_active, ext, st));
+      HIPCHK(poly_binop(POLY_SCALE, pk.l_active, nullptr, fr_neg_one(), pk.l_active, ext, st));
+    }
   }
   // permutation: Assembly on the host, sigma polynomials on the device
   HIPCHK(vec_alloc(pk.sigma_lag, pk.cs.P, n));
   HIPCHK(vec_alloc(pk.sigma_poly, pk.cs.P, n));
-  HIPCHK(vec_alloc(pk.sigma_coset, pk.cs.P, ext));
+  HIPCHK(vec_alloc(pk.sigma_coset, pk.cs.P, clen));
   if (pk.cs.P && img) {
     for (int i = 0; i < pk.cs.P; i++) {
       HIPCHK(img->upload(pk.sigma_lag[i], img->sigma_lag[i], n, st));
       HIPCHK(img->upload(pk.sigma_poly[i], img->sigma_poly[i], n, st));
-      HIPCHK(img->upload(pk.sigma_coset[i], img->sigma_coset[i], ext, st));
+      RCCHK(image_coset(pk.sigma_coset[i], img->sigma_coset[i]));
     }
     HIPCHK(hipStreamSynchronize(st));
   } else if (pk.cs.P) {
@@ -588,7 +623,7 @@ int keygen_impl(Device* d, Params& prm, const h2g_circuit* c, ProvingKey& pk, co
     for (int i = 0; i < pk.cs.P; i++) {
       HIPCHK(sigma_from_mapping(pk.sigma_lag[i], dmc + i * n, dmr + i * n, n, ddp, pk.om, st));
       RCCHK(lagrange_to_coeff(d, pk.dom, pk.sigma_lag[i], pk.sigma_poly[i], st));
-      RCCHK(coeff_to_extended(d, pk.dom, pk.sigma_poly[i], pk.sigma_coset[i], st));
+      if (!streamed) RCCHK(coeff_to_extended(d, pk.dom, pk.sigma_poly[i], pk.sigma_coset[i], st));
     }
     HIPCHK(hipStreamSynchronize(st));
     (void)hipFree(dmc);
@@ -657,12 +692,19 @@ int keygen_impl(Device* d, Params& prm, const h2g_circuit* c, ProvingKey& pk, co
 extern "C" {
 
 int h2g_keygen(uint64_t params, const h2g_circuit* circuit, uint64_t* pk_out) {
+  return h2g_keygen_opts(params, circuit, nullptr, pk_out);
+}
+
+int h2g_keygen_opts(uint64_t params, const h2g_circuit* circuit, const h2g_key_options* opts, uint64_t* pk_out) {
   NEED_DEV_P();
   Params* it = find_params(params);
   if (!it) return fail(H2G_ERR_HANDLE, "unknown params");
   if (!circuit || !pk_out) return fail(H2G_ERR_ARG, "keygen: null argument");
+  int cosets = H2G_COSETS_RESIDENT;
+  RCCHK(key_options_mode(opts, "keygen", &cosets));
   auto pk = std::make_unique<ProvingKey>();
   pk->params = params;
+  pk->cosets = cosets;
   int rc = keygen_impl(d, *it, circuit, *pk);
   // the lookup commitments' basis (params_prefix) now, not inside the first proof
   if (!rc && circuit->num_lookups > 0) rc = params_prefix(*it, d->stream);
@@ -731,6 +773,42 @@ int h2g_pk_info(uint64_t pk, int32_t info[8]) {
   const int32_t v[8] = {p.cs.degree, p.cs.bf, (int32_t)p.dom.ek, p.cs.nsets, (int32_t)p.cs.adv_q.size(),
                         (int32_t)p.cs.fix_q.size(), (int32_t)p.cs.ins_q.size(), p.n_slots};
   std::memcpy(info, v, sizeof(v));
+  return H2G_OK;
+}
+
+/* out[0] the coset mode, out[1] the device bytes the key holds now (its arrays and the
+ * per-proof workspaces grown so far), out[2] those of them in arrays of 2^extended_k
+ * elements, out[3] 0.  The extended arrays are counted from the key's shape: h_ext, h_coeff
+ * and (once allocated) h_gather in either mode -- the multi-open workspaces hold none --
+ * and, resident only, one per coset column of the key and of every circuit workspace, plus
+ * whatever the SPMD sub-coset split cut from them. */
+int h2g_pk_memory(uint64_t pk_h, uint64_t out[4]) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  ProvingKey* it = find_pk(pk_h);
+  if (!it) return fail(H2G_ERR_HANDLE, "unknown proving key");
+  if (!out) return fail(H2G_ERR_ARG, "pk_memory: null output");
+  const ProvingKey& p = *it;
+  uint64_t total = p.pool.bytes;
+  for (const auto& w : p.cws) total += w->pool.bytes;
+  total += p.lk_counters.len * sizeof(uint32_t) + p.lk_flags.len + p.lk_diff.len * sizeof(Fr) +
+           p.lk_or_d.len * sizeof(unsigned long long) + p.wsum_d.len * sizeof(unsigned long long) +
+           p.d_reqs.len * sizeof(EvalReq) + (p.evals.len + p.eval_scr.len + p.cs_scr.len + p.perm_lz.len) * sizeof(Fr) +
+           p.lkb_canon.len * sizeof(CanonKey) + (p.lkb_key[0].len + p.lkb_key[1].len) * sizeof(uint64_t) +
+           (p.lkb_idx[0].len + p.lkb_idx[1].len) * sizeof(uint32_t) + p.lkb_scr.len +
+           (p.slab_buf.len + p.x_send.len + p.x_recv.len + p.blind_d.len) * sizeof(Fr) +
+           p.d_segs.len * sizeof(CopySeg) + p.d_seeds.len * sizeof(uint32_t) + p.d_offsets.len * sizeof(uint64_t);
+  uint64_t ext_arrays = 2 + (p.h_gather ? 1 : 0);  // h_ext, h_coeff, h_gather
+  if (!p.cosets) {
+    const uint64_t per_ws = (uint64_t)p.cs.A + p.cs.I + p.cs.nsets + 3 * (uint64_t)p.cs.NL + p.cs.NS;
+    ext_arrays += (uint64_t)p.cs.F + p.cs.P + 3 + per_ws * p.cws.size();
+    for (const Fr* s : p.sub_fixed) ext_arrays += s != nullptr;
+    for (const Fr* s : p.sub_sigma) ext_arrays += s != nullptr;
+    ext_arrays += (p.sub_l0 != nullptr) + (p.sub_ll != nullptr) + (p.sub_la != nullptr);
+  }
+  out[0] = (uint64_t)p.cosets;
+  out[1] = total;
+  out[2] = ext_arrays * p.ext * sizeof(Fr);
+  out[3] = 0;
   return H2G_OK;
 }
 

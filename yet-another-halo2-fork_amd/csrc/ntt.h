@@ -64,6 +64,18 @@ struct NttArgs {
   Fr scale;
   int out_distribute = 0;
   Fr out_z1, out_z2;
+  // geometric input twist, fused into the first pass: x_i = src[i] * zeta^(i mod 3) * g^i
+  // (in_z1 = zeta, in_z2 = zeta^2; in_distribute is implied).  g = tw_g = root^tw_mul for
+  // the root whose powers the two-level table holds: root^i = tw_lo[i & (2^tw_bits - 1)] *
+  // tw_hi[i >> tw_bits], i <= tw_mask (the root's order - 1).  The kernels form the factors
+  // themselves -- one table power per thread, then a running product -- so no table of N
+  // factors exists per g.
+  int in_twist = 0;
+  Fr tw_g;
+  const Fr* tw_lo = nullptr;
+  const Fr* tw_hi = nullptr;
+  int tw_bits = 0;
+  uint64_t tw_mul = 0, tw_mask = 0;
 };
 
 void ntt_split(int L, int* P, int lg[NTT_MAX_PASSES]);

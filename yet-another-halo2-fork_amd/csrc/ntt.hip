@@ -181,13 +181,32 @@ struct NttConst29 {
   F29 mul[3];      // epilogue multiplier per y mod 3 (last pass), one29 when none
 };
 
+// The geometric input twist of a first pass (NttArgs::in_twist): x_j = src[j] gamma^j with
+// gamma = zeta g (zeta^3 = 1, so zeta^(j mod 3) = zeta^j).  A lane's eight inputs sit
+// 2^(L-3) apart, so it forms gamma^j for its first one -- g^j from the caller's two-level
+// power table (root^(mul j)), times the zeta power -- and walks to the others with one
+// product by `step` = gamma^(2^(L-3)) each.  No table of n factors per g.
+struct NttTwist29 {
+  const Fr* lo;    // root^i, i < 2^bits
+  const Fr* hi;    // root^(i 2^bits)
+  int bits;
+  uint64_t mul;    // g = root^mul
+  uint64_t mask;   // the root's order - 1
+  F29 step;
+};
+
 // (Inter-pass twiddles formed in the pass from the two-level table -- one product and two
 // L2-resident loads per element -- instead of streamed from pass_tw, 32 B of HBM per
 // element: measured, rejected.)
-template <int M>
+// TWIST is a compile-time variant (the first pass, out of place: first = 1, lrem = L): the
+// plain instantiations hold nothing of it, their `twist` is an empty struct.
+struct NttNoTwist {};
+template <bool TWIST>
+using NttTwistArg29 = std::conditional_t<TWIST, NttTwist29, NttNoTwist>;
+template <int M, bool TWIST = false>
 __global__ void __launch_bounds__(NTT_THREADS, NttPassWaves<M>::value)
 ntt_pass29_kernel(Fr* data, NttIo io, int first, uint64_t n_in, NttTables tab, const Fr* __restrict__ ptw, int L,
-                  int lrem, int distribute, NttConst29 k29) {
+                  int lrem, int distribute, NttConst29 k29, NttTwistArg29<TWIST> twist) {
   using D = WaveDif29<M>;
   data += (uint64_t)blockIdx.y << L;
   const Fr* in = first ? io.src[blockIdx.y] : nullptr;
@@ -204,25 +223,46 @@ ntt_pass29_kernel(Fr* data, NttIo io, int first, uint64_t n_in, NttTables tab, c
   const uint64_t base = (q << lrem) + g * D::CPW;
   const int c = lane % D::CPW, rg = lane / D::CPW;
   F29 x[8];
-  sfor<0, 8>([&](auto qc) {
-    constexpr int qq = decltype(qc)::value;
-    const uint64_t pos = base + c + (uint64_t)(rg + D::LPC * qq) * S;
-    if (in) {
+  if constexpr (TWIST) {
+    // f = gamma^pos of register 0: to29 of the storage-form power is its F29 element (an
+    // integer < 32 M, a valid factor); every later f is a product, < 1.2 M, and so is
+    // every input (stored values < 3 M hold).  The loads go first, the chain under them.
+    const uint64_t p0 = base + c + (uint64_t)rg * S;
+    const uint64_t e = (twist.mul * p0) & twist.mask;
+    const uint32_t md = mod3(p0);
+    F29 f = mul29<FrParams>(to29(twist.lo[e & ((1ull << twist.bits) - 1)] * twist.hi[e >> twist.bits]),
+                            sel29(md == 1, k29.z1, sel29(md == 2, k29.z2, one29v<FrParams>())));
+    sfor<0, 8>([&](auto qc) {
+      constexpr int qq = decltype(qc)::value;
+      const uint64_t pos = p0 + (uint64_t)(D::LPC * qq) * S;
       F29 v;
 #pragma unroll
       for (int i = 0; i < 9; i++) v.l[i] = 0;
-      if (pos < n_in) {
-        v = ld29(in + pos);
-        if (distribute) {
-          const uint32_t md = mod3(pos);
-          if (md) v = mul29<FrParams>(v, sel29(md == 1, k29.z1, k29.z2));
-        }
-      }
+      if (pos < n_in) v = mul29<FrParams>(ld29(in + pos), f);
       x[qq] = v;
-    } else {
-      x[qq] = ld29(data + pos);
-    }
-  });
+      if constexpr (qq < 7) f = mul29<FrParams>(f, twist.step);
+    });
+  } else {
+    sfor<0, 8>([&](auto qc) {
+      constexpr int qq = decltype(qc)::value;
+      const uint64_t pos = base + c + (uint64_t)(rg + D::LPC * qq) * S;
+      if (in) {
+        F29 v;
+#pragma unroll
+        for (int i = 0; i < 9; i++) v.l[i] = 0;
+        if (pos < n_in) {
+          v = ld29(in + pos);
+          if (distribute) {
+            const uint32_t md = mod3(pos);
+            if (md) v = mul29<FrParams>(v, sel29(md == 1, k29.z1, k29.z2));
+          }
+        }
+        x[qq] = v;
+      } else {
+        x[qq] = ld29(data + pos);
+      }
+    });
+  }
   D::run(x, w, rg);
   const uint64_t ilow = g * D::CPW + c;
   sfor<0, 8>([&](auto qc) {
@@ -411,10 +451,22 @@ ntt_last29_kernel(const Fr* data, NttIo io, uint64_t out_len, NttTables tab, int
 
 // ---------------------------------------------------------------------------
 // Whole transform in one block (N <= 2^NTT_SMALL_MAX_LOG), radix-2 DIF in LDS.
+// The geometric input twist here (NttArgs::in_twist, cf. NttTwist29): thread i walks
+// i, i + 256, ... with one product by step = gamma^256 each.
+struct NttTwistFr {
+  const Fr* lo;
+  const Fr* hi;
+  int bits;
+  uint64_t mul, mask;
+  Fr step;
+};
+template <bool TWIST>
+using NttTwistArgFr = std::conditional_t<TWIST, NttTwistFr, NttNoTwist>;
+template <bool TWIST>
 __global__ void __launch_bounds__(256)
 ntt_small_kernel(NttIo io, uint64_t n_in, uint64_t out_len, NttTables tab, int L,
                  int in_distribute, Fr iz1, Fr iz2, int has_scale, Fr scale, int out_distribute,
-                 Fr oz1, Fr oz2) {
+                 Fr oz1, Fr oz2, NttTwistArgFr<TWIST> tw) {
   const Fr* src = io.src[blockIdx.x];
   Fr* out = io.dst[blockIdx.x];
   extern __shared__ __align__(16) unsigned char smem_raw[];
@@ -422,17 +474,31 @@ ntt_small_kernel(NttIo io, uint64_t n_in, uint64_t out_len, NttTables tab, int L
   const int N = 1 << L;
   Fr* w = s + N;
   for (int j = threadIdx.x; j < N / 2; j += blockDim.x) w[j] = twiddle(tab, (uint64_t)j);
-  for (int i = threadIdx.x; i < N; i += blockDim.x) {
-    Fr v = Fr::zero();
-    if ((uint64_t)i < n_in) {
-      v = ld_fr(src + i);
-      if (in_distribute) {
-        const int md = i % 3;
-        if (md == 1) v = v * iz1;
-        else if (md == 2) v = v * iz2;
+  if constexpr (TWIST) {
+    if ((int)threadIdx.x < N) {
+      const uint64_t e = (tw.mul * threadIdx.x) & tw.mask;
+      Fr f = tw.lo[e & ((1ull << tw.bits) - 1)] * tw.hi[e >> tw.bits];
+      const int md = threadIdx.x % 3;
+      if (md == 1) f = f * iz1;
+      else if (md == 2) f = f * iz2;
+      for (int i = threadIdx.x; i < N; i += blockDim.x) {
+        s[i] = (uint64_t)i < n_in ? ld_fr(src + i) * f : Fr::zero();
+        f = f * tw.step;
       }
     }
-    s[i] = v;
+  } else {
+    for (int i = threadIdx.x; i < N; i += blockDim.x) {
+      Fr v = Fr::zero();
+      if ((uint64_t)i < n_in) {
+        v = ld_fr(src + i);
+        if (in_distribute) {
+          const int md = i % 3;
+          if (md == 1) v = v * iz1;
+          else if (md == 2) v = v * iz2;
+        }
+      }
+      s[i] = v;
+    }
   }
   __syncthreads();
   for (int hlog = L - 1; hlog >= 0; hlog--) {
@@ -562,8 +628,21 @@ void ntt_free_tables(NttTables* t) {
 }
 
 hipError_t ntt_init_attributes() {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(&ntt_small_kernel),
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ntt_small_kernel<false>),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  if (e != hipSuccess) return e;
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(&ntt_small_kernel<true>),
                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+}
+
+// the twisted first pass: never the sparse kernel (n_in = N), never a later pass
+template <int M>
+static void launch_pass_tw(const NttArgs& a, const NttIo& io, int B, int L, const NttConst29& k29,
+                           const NttTwist29& tw, hipStream_t st) {
+  const uint64_t waves = (1ull << L) / ((1ull << M) * WaveDif29<M>::CPW);
+  const unsigned blocks = (unsigned)((waves + NTT_WAVES - 1) / NTT_WAVES);
+  hipLaunchKernelGGL((ntt_pass29_kernel<M, true>), dim3(blocks, (unsigned)B), dim3(NTT_THREADS), 0, st, a.work, io, 1,
+                     a.n_in, a.tab, (const Fr*)(a.tab.pass_tw + a.tab.pass_off[0]), L, L, 1, k29, tw);
 }
 
 template <int M>
@@ -586,8 +665,9 @@ static void launch_pass(const NttArgs& a, const NttIo& io, int B, int p, int fir
                        (const Fr*)(a.tab.pass_tw + a.tab.pass_off[p]), L, lrem, waves);
     return;
   }
-  hipLaunchKernelGGL(ntt_pass29_kernel<M>, dim3(blocks, (unsigned)B), dim3(NTT_THREADS), 0, st, a.work, io, first,
-                     n_in, a.tab, (const Fr*)(a.tab.pass_tw + a.tab.pass_off[p]), L, lrem, dist, k29);
+  hipLaunchKernelGGL((ntt_pass29_kernel<M, false>), dim3(blocks, (unsigned)B), dim3(NTT_THREADS), 0, st, a.work, io,
+                     first, n_in, a.tab, (const Fr*)(a.tab.pass_tw + a.tab.pass_off[p]), L, lrem, dist, k29,
+                     NttNoTwist{});
 }
 
 hipError_t ntt_run(const NttArgs& a, hipStream_t st) {
@@ -605,11 +685,21 @@ hipError_t ntt_run(const NttArgs& a, hipStream_t st) {
   ntt_split(L, &plan.p, plan.lg);
   const int P = plan.p;
   const int* lg = plan.lg;
+  if (a.in_twist && (!a.tw_lo || !a.tw_hi || a.n_in > N)) return hipErrorInvalidValue;
+  // gamma = zeta g, the twist's ratio (in_z1 = zeta)
+  const Fr gamma = a.in_twist ? a.tw_g * a.in_z1 : Fr::one();
+  if (P == 1 && a.in_twist) {
+    const size_t sm = (N + N / 2 + 1) * sizeof(Fr);
+    NttTwistFr tw = {a.tw_lo, a.tw_hi, a.tw_bits, a.tw_mul, a.tw_mask, pow_u64(gamma, 256)};
+    hipLaunchKernelGGL(ntt_small_kernel<true>, dim3((unsigned)B), dim3(256), sm, st, io, a.n_in, out_len, a.tab, L, 1,
+                       a.in_z1, a.in_z2, a.has_scale, a.scale, a.out_distribute, a.out_z1, a.out_z2, tw);
+    return hipGetLastError();
+  }
   if (P == 1) {
     const size_t sm = (N + N / 2 + 1) * sizeof(Fr);
-    hipLaunchKernelGGL(ntt_small_kernel, dim3((unsigned)B), dim3(256), sm, st, io, a.n_in, out_len, a.tab, L,
+    hipLaunchKernelGGL(ntt_small_kernel<false>, dim3((unsigned)B), dim3(256), sm, st, io, a.n_in, out_len, a.tab, L,
                        a.in_distribute, a.in_z1, a.in_z2, a.has_scale, a.scale, a.out_distribute, a.out_z1,
-                       a.out_z2);
+                       a.out_z2, NttNoTwist{});
     return hipGetLastError();
   }
   if (P > NTT_MAX_PASSES || lg[P - 1] != 6 || !a.tab.pass_tw) return hipErrorInvalidValue;
@@ -636,6 +726,19 @@ hipError_t ntt_run(const NttArgs& a, hipStream_t st) {
     const int first = p == 0;
     const uint64_t nin = first ? a.n_in : 0;
     const int dist = first ? a.in_distribute : 0;
+    if (first && a.in_twist) {
+      NttTwist29 tw = {a.tw_lo, a.tw_hi, a.tw_bits, a.tw_mul, a.tw_mask,
+                       storage_to_f29<FrParams>(pow_u64(gamma, 1ull << (L - 3)))};
+      switch (lg[0]) {
+        case 3: launch_pass_tw<3>(a, io, B, L, k29, tw, st); break;
+        case 4: launch_pass_tw<4>(a, io, B, L, k29, tw, st); break;
+        case 5: launch_pass_tw<5>(a, io, B, L, k29, tw, st); break;
+        case 6: launch_pass_tw<6>(a, io, B, L, k29, tw, st); break;
+        default: return hipErrorInvalidValue;
+      }
+      lrem -= lg[0];
+      continue;
+    }
     switch (lg[p]) {
       case 3: launch_pass<3>(a, io, B, p, first, nin, L, lrem, dist, k29, st); break;
       case 4: launch_pass<4>(a, io, B, p, first, nin, L, lrem, dist, k29, st); break;

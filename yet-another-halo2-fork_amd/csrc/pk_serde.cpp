@@ -374,15 +374,34 @@ int h2g_pk_write(uint64_t pk_h, int format, uint8_t* out, size_t cap, size_t* le
   ByteWriter w{out, out ? cap : 0, d->stream};
   w.proc = format == SERDE_PROCESSED;
   vk_write_prefix(w, pk.cs.k, pk.vk_fixed, pk.vk_perm);
-  RCCHK(w.poly(pk.l0, pk.ext));
-  RCCHK(w.poly(pk.l_last, pk.ext));
-  RCCHK(w.poly(pk.l_active, pk.ext));
+  // The format holds the extended cosets.  A streamed key has none: each is produced from
+  // its polynomial in the h(X) buffer (free between proofs) and written from there, one at a
+  // time -- the same field elements a resident key holds, so the same bytes.
+  auto coset = [&](const Fr* resident, const Fr* coeffs) -> int {
+    if (!pk.cosets) return w.poly(resident, pk.ext);
+    if (w.out) RCCHK(coeff_to_extended(d, pk.dom, coeffs, pk.h_ext, d->stream));
+    return w.poly(pk.h_ext, pk.ext);
+  };
+  auto cosets = [&](const std::vector<Fr*>& resident, const std::vector<Fr*>& coeffs) -> int {
+    w.u32be((uint32_t)resident.size());
+    for (size_t i = 0; i < resident.size(); i++) RCCHK(coset(resident[i], coeffs[i]));
+    return H2G_OK;
+  };
+  RCCHK(coset(pk.l0, pk.l0_poly));
+  RCCHK(coset(pk.l_last, pk.l_last_poly));
+  if (pk.cosets && w.out) {  // l_active = -((l_last + l_blind) - 1), in coefficient form (pk.mod)
+    const Fr one = Fr::one();
+    HIPCHK(poly_binop(POLY_ADD, pk.l_last_poly, pk.l_blind_poly, one, pk.mod, pk.n, d->stream));
+    HIPCHK(poly_binop(POLY_SUB_CONST, pk.mod, nullptr, one, pk.mod, 1, d->stream));
+    HIPCHK(poly_binop(POLY_SCALE, pk.mod, nullptr, fr_neg_one(), pk.mod, pk.n, d->stream));
+  }
+  RCCHK(coset(pk.l_active, pk.mod));
   RCCHK(w.polys(pk.fixed_lag, pk.n));
   RCCHK(w.polys(pk.fixed_poly, pk.n));
-  RCCHK(w.polys(pk.fixed_coset, pk.ext));
+  RCCHK(cosets(pk.fixed_coset, pk.fixed_poly));
   RCCHK(w.polys(pk.sigma_lag, pk.n));  // permutation::ProvingKey::write (permutation.rs:82-91)
   RCCHK(w.polys(pk.sigma_poly, pk.n));
-  RCCHK(w.polys(pk.sigma_coset, pk.ext));
+  RCCHK(cosets(pk.sigma_coset, pk.sigma_poly));
   *len = w.len;
   if (out && w.len > cap) return fail(H2G_ERR_ARG, "pk_write: buffer too small");
   return H2G_OK;
@@ -393,7 +412,17 @@ int h2g_pk_write(uint64_t pk_h, int format, uint8_t* out, size_t cap, size_t* le
  * (circuit->fixed_values and ->copies are not used and may be NULL). */
 int h2g_pk_read(uint64_t params, const h2g_circuit* circuit, const uint8_t* buf, size_t len, int format,
                 uint64_t* pk_out) {
+  return h2g_pk_read_opts(params, circuit, buf, len, format, nullptr, pk_out);
+}
+
+/* The same with key options.  A streamed key takes the file's polynomials, runs every check
+ * of the resident read on the file's cosets (in scratch, array by array) and drops them:
+ * its proofs derive the sub-cosets from the polynomials. */
+int h2g_pk_read_opts(uint64_t params, const h2g_circuit* circuit, const uint8_t* buf, size_t len, int format,
+                     const h2g_key_options* opts, uint64_t* pk_out) {
   NEED_DEV_P();
+  int cosets = H2G_COSETS_RESIDENT;
+  RCCHK(key_options_mode(opts, "pk_read", &cosets));
   Params* it = find_params(params);
   if (!it) return fail(H2G_ERR_HANDLE, "unknown params");
   if (!circuit || !buf || !pk_out) return fail(H2G_ERR_ARG, "pk_read: null argument");
@@ -433,8 +462,15 @@ int h2g_pk_read(uint64_t params, const h2g_circuit* circuit, const uint8_t* buf,
     HIPCHK(hipMemsetAsync(bad.p, 0, 4, d->stream));
     img.bad = (uint32_t*)bad.p;
   }
+  DevScratch bad_raw;
+  if (cosets && format == SERDE_RAW) {
+    HIPCHK(hipMalloc(&bad_raw.p, 4));
+    HIPCHK(hipMemsetAsync(bad_raw.p, 0, 4, d->stream));
+    img.bad_raw = (uint32_t*)bad_raw.p;
+  }
   auto pk = std::make_unique<ProvingKey>();
   pk->params = params;
+  pk->cosets = cosets;
   int rc = keygen_impl(d, *it, circuit, *pk, &img);
   if (rc == H2G_OK && proc) {
     uint32_t nbad = 0;
@@ -445,19 +481,26 @@ int h2g_pk_read(uint64_t params, const h2g_circuit* circuit, const uint8_t* buf,
   }
   if (rc == H2G_OK && pk->ext != ext_len) rc = fail(H2G_ERR_ARG, "pk_read: extended domain size does not match the circuit");
   if (rc == H2G_OK && format == SERDE_RAW) {
-    std::vector<std::pair<const Fr*, size_t>> arrays = {{pk->l0, pk->ext}, {pk->l_last, pk->ext}, {pk->l_active, pk->ext}};
+    // (a streamed key counted its cosets as they passed through scratch: img.bad_raw)
+    std::vector<std::pair<const Fr*, size_t>> arrays;
+    if (!cosets) arrays = {{pk->l0, pk->ext}, {pk->l_last, pk->ext}, {pk->l_active, pk->ext}};
     for (int i = 0; i < pk->cs.F; i++) {
       arrays.push_back({pk->fixed_lag[i], n});
       arrays.push_back({pk->fixed_poly[i], n});
-      arrays.push_back({pk->fixed_coset[i], pk->ext});
+      if (!cosets) arrays.push_back({pk->fixed_coset[i], pk->ext});
     }
     for (int i = 0; i < pk->cs.P; i++) {
       arrays.push_back({pk->sigma_lag[i], n});
       arrays.push_back({pk->sigma_poly[i], n});
-      arrays.push_back({pk->sigma_coset[i], pk->ext});
+      if (!cosets) arrays.push_back({pk->sigma_coset[i], pk->ext});
     }
-    uint32_t nbad = 0;
+    uint32_t nbad = 0, nbad_dropped = 0;
     rc = count_bad_fr(arrays, d->stream, &nbad);
+    if (rc == H2G_OK && img.bad_raw) {
+      if (hipMemcpy(&nbad_dropped, img.bad_raw, 4, hipMemcpyDeviceToHost) != hipSuccess)
+        rc = fail(H2G_ERR_DEVICE, "pk_read: counter copy");
+      nbad += nbad_dropped;
+    }
     if (rc == H2G_OK && nbad) rc = fail(H2G_ERR_ARG, "pk_read: " + std::to_string(nbad) + " field elements not below the modulus");
   }
   if (rc) return rc;

@@ -432,6 +432,7 @@ struct ProofRun {
   int lookup_shuffle_products();
   int vanishing_commit();
   int eval_h();
+  int eval_h_streamed();
   int h_commit();
   int openings_and_evals();
   MultiopenCtx multiopen_ctx();
@@ -1321,6 +1322,7 @@ int ProofRun::vanishing_commit() {
 // previous circuit's Horner chain in y; the last one divides by t(X)
 int ProofRun::eval_h() {
   const bool subc = spmd_subcosets();
+  if (pk.cosets) return eval_h_streamed();
   for (int ci = 0; ci < ncirc && !subc; ci++) {
     const CircuitWs& w = *W[ci];
     EvalHArgs a = eval_h_args(ci);
@@ -1390,6 +1392,75 @@ int ProofRun::eval_h() {
     }
   }
   if (!h_slabs) dump("h_ext", pk.h_ext, ext, st);
+  clk.mark("evaluate_h");
+  return H2G_OK;
+}
+
+// A streamed key (ProvingKey::cosets): the same evaluation sub-coset by sub-coset.  Row
+// t + 2^e m of the extended coset is the point zeta w_ext^t w^m and rotations move rows by
+// multiples of 2^e, so evaluate_h on sub-coset t reads sub-coset t of every column -- the
+// arguments the SPMD split passes -- and every column array is one n-point slot, refilled for
+// each t from its coefficient form: the key's columns once per t for all circuits, then
+// circuit by circuit (the slots are shared, so a circuit's transforms follow the previous
+// circuit's launch).  All on the prover's stream, one slot set: the transforms and the
+// launches alternate, each filling the chip on its own (DESIGN, "Streamed cosets").
+int ProofRun::eval_h_streamed() {
+  const int e = (int)(D.ek - D.k);
+  const Fr one = Fr::one();
+  std::vector<const Fr*> ksrc;
+  std::vector<Fr*> kdst;
+  for (int i = 0; i < pk.cs.F; i++) ksrc.push_back(pk.fixed_poly[i]), kdst.push_back(pk.fixed_coset[i]);
+  for (int i = 0; i < pk.cs.P; i++) ksrc.push_back(pk.sigma_poly[i]), kdst.push_back(pk.sigma_coset[i]);
+  ksrc.push_back(pk.l0_poly), kdst.push_back(pk.l0);
+  ksrc.push_back(pk.l_last_poly), kdst.push_back(pk.l_last);
+  ksrc.push_back(pk.l_blind_poly), kdst.push_back(pk.l_active);  // l_blind, then 1 - l_last - l_blind in place
+  std::vector<std::vector<const Fr*>> csrc(ncirc);
+  std::vector<std::vector<Fr*>> cdst(ncirc);
+  for (int ci = 0; ci < ncirc; ci++) {
+    const CircuitWs& w = *W[ci];
+    auto add = [&](const std::vector<Fr*>& polys, const std::vector<Fr*>& slots) {
+      for (size_t i = 0; i < polys.size(); i++) csrc[ci].push_back(polys[i]), cdst[ci].push_back(slots[i]);
+    };
+    add(w.adv_poly, w.adv_coset);
+    add(w.inst_poly, w.inst_coset);
+    add(w.z, w.z_coset);
+    add(w.lk_ap_poly, w.lk_apc);
+    add(w.lk_sp_poly, w.lk_spc);
+    add(w.lk_z_poly, w.lk_zc);
+    add(w.sh_z_poly, w.sh_zc);
+  }
+  for (uint64_t t = 0; t < (1ull << e); t++) {
+    RCCHK(coeff_to_subcoset_batch(d, D, ksrc.data(), kdst.data(), (int)ksrc.size(), t, st));
+    HIPCHK(poly_binop(POLY_ADD, pk.l_last, pk.l_active, one, pk.l_active, n, st));
+    HIPCHK(poly_binop(POLY_SUB_CONST, pk.l_active, nullptr, one, pk.l_active, n, st));
+    HIPCHK(poly_binop(POLY_SCALE, pk.l_active, nullptr, fr_neg_one(), pk.l_active, n, st));
+    Fr* slot = pk.h_gather + t * n;
+    for (int ci = 0; ci < ncirc; ci++) {
+      const CircuitWs& w = *W[ci];
+      RCCHK(coeff_to_subcoset_batch(d, D, csrc[ci].data(), cdst[ci].data(), (int)csrc[ci].size(), t, st));
+      EvalHArgs a = eval_h_args(ci);
+      a.lookups = w.d_lookups;  // the tables of circuit_ws_add: their columns are the slots
+      a.shuffles = w.d_shuffles;
+      a.query_col = w.d_load_col;
+      a.z = w.d_z;
+      a.perm_v = w.d_perm_v;
+      a.sigma = pk.d_sigma;
+      a.l0 = pk.l0;
+      a.l_last = pk.l_last;
+      a.l_active = pk.l_active;
+      a.delta_start = beta * zeta() * pow_u64(D.ext_omega, t);  // X = zeta w_ext^t w^m
+      a.ext_omega = pk.om;
+      a.ext = n;
+      a.rot_scale = 1;
+      a.t_evals = D.d_t.p + t;  // t(X) is constant on a sub-coset
+      a.t_mask = 0;
+      a.acc_in = ci > 0 ? slot : nullptr;
+      a.out = slot;
+      HIPCHK(evaluate_h(a, st));
+    }
+  }
+  HIPCHK(subcoset_scatter(pk.h_gather, pk.h_ext, n, e, st));
+  dump("h_ext", pk.h_ext, ext, st);
   clk.mark("evaluate_h");
   return H2G_OK;
 }
@@ -1603,6 +1674,9 @@ int ProofRun::shplonk() {
 // priorities (transforms low, or MSMs high) measured slower (profiles/r06/xs/).
 int prove_impl(Device* d, Params& prm, ProvingKey& pk, const ProveIn& in, std::vector<uint8_t>* proof) {
   hipStream_t st = d->stream;
+  if (pk.cosets && g_spmd.world > 1)
+    return fail(H2G_ERR_STATE, "create_proof: a streamed-coset key does not prove under an SPMD transport of " +
+                                   std::to_string(g_spmd.world) + " ranks (make the key with H2G_COSETS_RESIDENT)");
   xp_drain(pk);  // a failed proof's overlapped exchanges
   RCCHK(pk_upload_arm(pk, st));
   while ((int)pk.cws.size() < in.nc) RCCHK(circuit_ws_add(pk));  // workspaces grow once

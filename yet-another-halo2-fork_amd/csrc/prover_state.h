@@ -36,9 +36,13 @@ enum { OP_CONST = 0, OP_QUERY = 1, OP_NEG = 2, OP_SUM = 3, OP_PROD = 4, OP_CHALL
 
 struct Pool {  // owns device allocations of one params / pk object
   std::vector<void*> ptrs;
-  hipError_t get(void** p, size_t bytes) {
-    hipError_t e = hipMalloc(p, bytes ? bytes : 16);
-    if (e == hipSuccess) ptrs.push_back(*p);
+  uint64_t bytes = 0;  // requested, of the live allocations (h2g_pk_memory)
+  hipError_t get(void** p, size_t nbytes) {
+    hipError_t e = hipMalloc(p, nbytes ? nbytes : 16);
+    if (e == hipSuccess) {
+      ptrs.push_back(*p);
+      bytes += nbytes ? nbytes : 16;
+    }
     return e;
   }
   ~Pool() {
@@ -212,9 +216,18 @@ struct ProvingKey {
   size_t up_off = 0;
   Domain dom;
   Pool pool;
+  // H2G_COSETS_RESIDENT: every column evaluate_h reads is held as its extended coset (the
+  // *_coset arrays of the key and of each CircuitWs, l0 / l_last / l_active: 2^ek elements
+  // each).  H2G_COSETS_STREAMED: each of those arrays is one n-element slot; evaluate_h runs
+  // sub-coset by sub-coset (ProofRun::eval_h) and the slots are refilled from the coefficient
+  // forms for every sub-coset (coeff_to_subcoset_batch).  Set before keygen_impl.
+  int cosets = 0;
   // proving key (device)
   std::vector<Fr*> fixed_lag, fixed_poly, fixed_coset, sigma_lag, sigma_poly, sigma_coset;
   Fr *l0 = nullptr, *l_last = nullptr, *l_active = nullptr;
+  // streamed only: coefficient forms of l_0, l_last and l_blind (the sum of the blinding
+  // rows' Lagrange polynomials); on any set of points l_active = 1 - l_last - l_blind
+  Fr *l0_poly = nullptr, *l_last_poly = nullptr, *l_blind_poly = nullptr;
   PowTable om, eo;
   int4* prog = nullptr;
   int prog_len = 0, n_slots = 0;
@@ -423,6 +436,9 @@ struct PkImage {
   const uint8_t *l0 = nullptr, *l_last = nullptr, *l_active = nullptr;
   bool canonical = false;
   uint32_t* bad = nullptr;  // device counter, Processed only
+  // device counter of unreduced elements in the arrays a streamed key checks and drops (its
+  // cosets, SerdeFormat::RawBytes); null: no such check
+  uint32_t* bad_raw = nullptr;
   hipError_t upload(Fr* dst, const uint8_t* src, size_t cnt, hipStream_t st) const {
     hipError_t e = hipMemcpyAsync(dst, src, cnt * sizeof(Fr), hipMemcpyHostToDevice, st);
     if (e == hipSuccess && canonical) e = fr_from_repr(dst, cnt, bad, st);
@@ -464,6 +480,7 @@ int commit(Device* d, const Params& prm, const Fr* scalars, size_t n, int set, G
 // keygen.cpp
 int build_pow_table(Pool& pool, const Fr& w, int L, PowTable* t, hipStream_t st);
 int circuit_ws_add(ProvingKey& pk);
+int key_options_mode(const h2g_key_options* opts, const char* who, int* mode);
 int keygen_impl(Device* d, Params& prm, const h2g_circuit* c, ProvingKey& pk, const PkImage* img);
 
 // spmd.cpp

@@ -242,6 +242,10 @@ int lagrange_to_coeff_batch(Device* d, const Domain& dm, const Fr* const* src, F
 int coeff_to_extended_batch(Device* d, const Domain& dm, const Fr* const* src, Fr* const* dst, int count,
                             hipStream_t st);
 int extended_to_coeff(Device* d, const Domain& dm, const Fr* src, Fr* dst, hipStream_t st);
+// sub-coset t (< 2^(ek - k)) of each polynomial's extended coset, n points each: the rows
+// t + 2^(ek - k) m of coeff_to_extended, by an n-point transform with a fused input twist
+int coeff_to_subcoset_batch(Device* d, const Domain& dm, const Fr* const* src, Fr* const* dst, int count, uint64_t t,
+                            hipStream_t st);
 
 }  // namespace rt
 }  // namespace h2g

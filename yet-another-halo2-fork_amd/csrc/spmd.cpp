@@ -198,6 +198,7 @@ int sub_ws_tables(const ProvingKey& pk, CircuitWs& w) {
 // whole cosets, or under the SPMD sub-coset split this rank's sub-cosets (slot i of dst =
 // sub-coset sub_ts[i]; a rank past 2^e owns none and computes nothing)
 int ext_cosets(Device* d, const ProvingKey& pk, const Fr* const* src, Fr* const* dst, int count, hipStream_t st) {
+  if (pk.cosets) return H2G_OK;  // streamed: eval_h fills the slots from src, sub-coset by sub-coset
   if (!spmd_subcosets()) return coeff_to_extended_batch(d, pk.dom, src, dst, count, st);
   const size_t n = pk.n, nt = pk.sub_ts.size();
   std::vector<const Fr*> s2;

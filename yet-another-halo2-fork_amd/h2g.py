@@ -58,6 +58,9 @@ _SIGS = {
     "h2g_lagrange_to_coeff_dev": ([U64, VP, VP], I32),
     "h2g_coeff_to_extended": ([U64, U64P, U64P], I32),
     "h2g_coeff_to_extended_dev": ([U64, VP, VP, VP], I32),
+    "h2g_coeff_to_subcoset": ([U64, ctypes.POINTER(VP), I32, U64, ctypes.POINTER(VP)], I32),
+    "h2g_coeff_to_subcoset_dev": ([U64, ctypes.POINTER(VP), I32, U64, ctypes.POINTER(VP), VP], I32),
+    "h2g_debug_coeff_to_subcoset_unfused_dev": ([U64, ctypes.POINTER(VP), I32, U64, ctypes.POINTER(VP), VP], I32),
     "h2g_extended_to_coeff": ([U64, U64P, U64P], I32),
     "h2g_extended_to_coeff_dev": ([U64, VP, VP, VP], I32),
     "h2g_divide_by_vanishing_poly": ([U64, U64P], I32),
@@ -98,6 +101,9 @@ _SIGS = {
     "h2g_pk_write": ([U64, I32, VP, SZ, ctypes.POINTER(SZ)], I32),
     "h2g_pk_read": ([U64, VP, ctypes.c_char_p, SZ, I32, ctypes.POINTER(U64)], I32),
     "h2g_keygen": ([U64, VP, ctypes.POINTER(U64)], I32),
+    "h2g_keygen_opts": ([U64, VP, VP, ctypes.POINTER(U64)], I32),
+    "h2g_pk_read_opts": ([U64, VP, ctypes.c_char_p, SZ, I32, VP, ctypes.POINTER(U64)], I32),
+    "h2g_pk_memory": ([U64, ctypes.POINTER(U64)], I32),
     "h2g_pk_free": ([U64], I32),
     "h2g_pk_info": ([U64, ctypes.POINTER(ctypes.c_int32)], I32),
     "h2g_pk_vk_commitments": ([U64, U64P, U64P], I32),
@@ -416,6 +422,17 @@ class Domain:
         out = np.zeros((self.extended_len, 4), dtype=np.uint64)
         check(lib().h2g_coeff_to_extended(self.h, p64(a), p64(out)))
         return out
+
+    def coeff_to_subcoset(self, polys, t):
+        """Sub-coset t of every polynomial's extended coset: coeff_to_extended(p)[t::2^e], e =
+        extended_k - k, as (count, n, 4) -- n-point transforms, no extended array."""
+        polys = [np.ascontiguousarray(p, dtype=np.uint64) for p in polys]
+        assert all(p.shape == (self.n, 4) for p in polys)
+        outs = np.zeros((len(polys), self.n, 4), dtype=np.uint64)
+        src = (VP * max(1, len(polys)))(*[p.ctypes.data for p in polys])
+        dst = (VP * max(1, len(polys)))(*[outs[i].ctypes.data for i in range(len(polys))])
+        check(lib().h2g_coeff_to_subcoset(self.h, src, len(polys), t, dst))
+        return outs
 
     def extended_to_coeff(self, a):
         a = np.ascontiguousarray(a, dtype=np.uint64)
@@ -807,24 +824,49 @@ class Params:
             self.handle = 0
 
 
+COSETS = {"resident": 0, "streamed": 1}  # H2G_COSETS_*
+
+
+class KeyOptions(ctypes.Structure):  # h2g_key_options
+    _fields_ = [("size", U32), ("cosets", U32)]
+
+
 class ProvingKey:
     """keygen_vk + keygen_pk on the device for an h2g_circuit.Circuit."""
 
-    def __init__(self, params, circ, data=None, fmt=RAW_BYTES):
-        """keygen, or -- with `data` -- ProvingKey::read of serialised bytes (plonk.rs:334-359)"""
+    def __init__(self, params, circ, data=None, fmt=RAW_BYTES, cosets="resident"):
+        """keygen, or -- with `data` -- ProvingKey::read of serialised bytes (plonk.rs:334-359).
+        cosets="streamed": the key holds one n-point slot per column where a resident key holds
+        an extended coset (h2g_key_options); same proofs and key bytes, less device memory."""
+        if cosets not in COSETS:
+            raise ValueError(f"cosets must be one of {sorted(COSETS)}, not {cosets!r}")
         self.params = params
         self.circ = circ
+        self.cosets = cosets
         c, keep = _c_circuit(circ)
         h = U64()
-        if data is None:
+        opts = KeyOptions(ctypes.sizeof(KeyOptions), COSETS[cosets])
+        if data is None and cosets == "resident":
             check(lib().h2g_keygen(params.handle, ctypes.byref(c), ctypes.byref(h)))
-        else:
+        elif data is None:
+            check(lib().h2g_keygen_opts(params.handle, ctypes.byref(c), ctypes.byref(opts), ctypes.byref(h)))
+        elif cosets == "resident":
             check(lib().h2g_pk_read(params.handle, ctypes.byref(c), bytes(data), len(data), fmt, ctypes.byref(h)))
+        else:
+            check(lib().h2g_pk_read_opts(params.handle, ctypes.byref(c), bytes(data), len(data), fmt,
+                                         ctypes.byref(opts), ctypes.byref(h)))
         self.handle = h.value
         info = (ctypes.c_int32 * 8)()
         check(lib().h2g_pk_info(self.handle, info))
         (self.degree, self.bf, self.extended_k, self.nsets, self.n_adv_q, self.n_fix_q, self.n_ins_q,
          self.n_slots) = list(info)
+
+    def memory(self):
+        """h2g_pk_memory: the coset mode, the device bytes the key holds now (arrays and the
+        per-proof workspace grown so far) and how many of them are extended-domain arrays"""
+        out = (U64 * 4)()
+        check(lib().h2g_pk_memory(self.handle, out))
+        return {"cosets": "streamed" if out[0] else "resident", "bytes": int(out[1]), "ext_bytes": int(out[2])}
 
     def vk_commitments(self):
         """(fixed commitments, permutation commitments): uint64 arrays (F, 8), (P, 8) affine
