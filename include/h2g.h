@@ -590,6 +590,15 @@ int h2g_fr_eval_dev(const void* d_poly, size_t len, const uint64_t x[4], uint64_
  * asynchronous on `stream`, d_q must not overlap d_a, both 16-byte aligned. */
 int h2g_kate_division(const uint64_t* a, size_t len, const uint64_t b[4], uint64_t* q);
 int h2g_kate_division_dev(const void* d_a, size_t len, const uint64_t b[4], void* d_q, void* stream);
+/* test seam: h2g_kate_division_dev with the kernel variant chosen by the caller.  tile_s = the
+ * coefficients per thread, 8, 16, 32 or 64 (a tile is 256 tile_s quotients), 0 = by the size
+ * rule as h2g_kate_division_dev (another value: H2G_ERR_ARG).  accumulate != 0: d_q holds
+ * len - 1 reduced elements on entry and receives d_q + the quotient (SHPLONK's h(X) += ..). */
+int h2g_debug_kate_division_dev(const void* d_a, size_t len, const uint64_t b[4], void* d_q, int accumulate,
+                                int tile_s, void* stream);
+/* the size rule itself: the tile_s h2g_kate_division_dev takes for `len` coefficients (len == 0:
+ * H2G_ERR_ARG).  Host only: needs no h2g_init. */
+int h2g_debug_kate_tile_s(size_t len, int* tile_s);
 
 /* The multi-open argument.  A polynomial is in coefficient form, 1 <= len <= the params' n, in
  * host memory or (on_device) device memory, 16-byte aligned.  A query names its polynomial by

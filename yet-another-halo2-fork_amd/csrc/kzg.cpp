@@ -258,6 +258,27 @@ int h2g_kate_division_dev(const void* d_a, size_t len, const uint64_t b[4], void
   HIPCHK(kate_division((const Fr*)d_a, len, fr_from_limbs(b), (Fr*)d_q, d->work.as<Fr>(), pick_stream(d, stream)));
   return H2G_OK;
 }
+int h2g_debug_kate_division_dev(const void* d_a, size_t len, const uint64_t b[4], void* d_q, int accumulate,
+                                int tile_s, void* stream) {
+  NEED_DEV_P();
+  if (len == 0) return fail(H2G_ERR_ARG, "kate_division: an empty polynomial");
+  if (!d_a || !b || (len > 1 && !d_q)) return fail(H2G_ERR_ARG, "kate_division: null argument");
+  if ((uintptr_t)d_a % 16 || (uintptr_t)d_q % 16)
+    return fail(H2G_ERR_ARG, "kate_division: device arrays must be 16-byte aligned");
+  if (tile_s != 0 && tile_s != 8 && tile_s != 16 && tile_s != 32 && tile_s != 64)
+    return fail(H2G_ERR_ARG, "debug_kate_division: tile_s must be 0, 8, 16, 32 or 64");
+  if (len == 1) return H2G_OK;
+  HIPCHK(d->work.ensure(kate_scratch_len(len) * sizeof(Fr) + 32));
+  HIPCHK(kate_division((const Fr*)d_a, len, fr_from_limbs(b), (Fr*)d_q, d->work.as<Fr>(), pick_stream(d, stream),
+                       accumulate != 0, tile_s));
+  return H2G_OK;
+}
+int h2g_debug_kate_tile_s(size_t len, int* tile_s) {
+  if (len == 0) return fail(H2G_ERR_ARG, "kate_division: an empty polynomial");
+  if (!tile_s) return fail(H2G_ERR_ARG, "debug_kate_tile_s: null argument");
+  *tile_s = kate_tile_s((uint64_t)len - 1);
+  return H2G_OK;
+}
 int h2g_kate_division(const uint64_t* a, size_t len, const uint64_t b[4], uint64_t* q) {
   NEED_DEV_P();
   if (len == 0) return fail(H2G_ERR_ARG, "kate_division: an empty polynomial");

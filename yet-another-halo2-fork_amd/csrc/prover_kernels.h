@@ -238,9 +238,12 @@ size_t poly_eval_scratch_len(int nreq, uint64_t max_len);
 
 // ---- kate_division (arithmetic.rs:101-120): q = (a - a(b)) / (X - b), len(q) = len(a) - 1 ----
 // accumulate: q[0..len-1) += the quotient instead of =; scratch: kate_scratch_len(len)
+// force_s: 0 = coefficients per thread by kate_tile_s(len - 1); 8, 16, 32 or 64 runs that
+// variant at any length (test seam: h2g_debug_kate_division_dev, tests/test_gpu_scan_variants.py)
 hipError_t kate_division(const Fr* a, uint64_t len, const Fr& b, Fr* q, Fr* scratch, hipStream_t st,
-                         bool accumulate = false);
+                         bool accumulate = false, int force_s = 0);
 size_t kate_scratch_len(uint64_t len);
+int kate_tile_s(uint64_t M);  // the size rule: coefficients per thread for M = len - 1 quotients (host only)
 
 // ---- linear combinations: out[i] = (acc ? out[i] : 0) + sum_k coef_k * p_k[i] (i < len_k) ----
 static constexpr int LIN_MAXT = 12;

@@ -747,6 +747,7 @@ hipError_t poly_eval_batch(const EvalReq* d_reqs, int nreq, uint64_t max_len, Fr
 // KD_S (elements per thread) is chosen per call: the largest power of two in
 // [KD_S_MIN, KD_S_MAX] that still gives KD_MIN_BLOCKS tiles (longer chains amortise the
 // block scans and the one-block phase 2; a short polynomial keeps its blocks).
+// Every variant at any length, and the accumulating form: h2g_debug_kate_division_dev (kzg.cpp).
 #ifndef H2G_KD_S_MAX
 #define H2G_KD_S_MAX 32
 #endif
@@ -930,12 +931,19 @@ size_t kate_scratch_len(uint64_t len) {  // sized for the shortest tiles (KD_S_M
   return (size_t)(nt + 1 + nt * KD_T);
 }
 
-hipError_t kate_division(const Fr* a, uint64_t len, const Fr& b, Fr* q, Fr* scratch, hipStream_t st,
-                         bool accumulate) {
-  if (len < 2) return hipSuccess;
-  const uint64_t M = len - 1;
+int kate_tile_s(uint64_t M) {
   int S = KD_S_MIN;
   while (S < KD_S_MAX && (M + (uint64_t)KD_T * S * 2 - 1) / ((uint64_t)KD_T * S * 2) >= KD_MIN_BLOCKS) S <<= 1;
+  return S;
+}
+
+hipError_t kate_division(const Fr* a, uint64_t len, const Fr& b, Fr* q, Fr* scratch, hipStream_t st,
+                         bool accumulate, int force_s) {
+  if (len < 2) return hipSuccess;
+  const uint64_t M = len - 1;
+  // the scratch is sized for KD_S_MIN: a shorter forced tile would overrun it
+  if (force_s && force_s != 8 && force_s != 16 && force_s != 32 && force_s != 64) return hipErrorInvalidValue;
+  const int S = force_s ? force_s : kate_tile_s(M);
   const uint64_t tile_len = (uint64_t)KD_T * S;
   const uint64_t nt = (M + tile_len - 1) / tile_len;
   KatePow pw;

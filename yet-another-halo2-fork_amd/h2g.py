@@ -177,6 +177,8 @@ _SIGS = {
     "h2g_fr_eval_dev": ([VP, SZ, U64P, U64P, VP], I32),
     "h2g_kate_division": ([U64P, SZ, U64P, U64P], I32),
     "h2g_kate_division_dev": ([VP, SZ, U64P, VP, VP], I32),
+    "h2g_debug_kate_division_dev": ([VP, SZ, U64P, VP, I32, I32, VP], I32),
+    "h2g_debug_kate_tile_s": ([SZ, ctypes.POINTER(I32)], I32),
     "h2g_multiopen_prove": ([U64, I32, U64, VP, SZ, VP, SZ], I32),
     "h2g_multiopen_verify": ([VP, I32, U64, U64P, SZ, VP, SZ, ctypes.POINTER(ctypes.c_int32), U64P], I32),
     "h2g_pairing_check_batch": ([VP, U64P, SZ, ctypes.POINTER(ctypes.c_int32)], I32),
@@ -1393,6 +1395,20 @@ def kate_division(a, b):
 def kate_division_dev(d_a, n, b, d_q, stream=None):
     check(lib().h2g_kate_division_dev(VP(d_a), n, p64(np.ascontiguousarray(b, dtype=np.uint64)), VP(d_q),
                                       VP(stream) if stream else None))
+
+
+def debug_kate_division_dev(d_a, n, b, d_q, accumulate=False, tile_s=0, stream=None):
+    """h2g_debug_kate_division_dev (test seam): kate_division_dev by the variant with tile_s
+    coefficients per thread (8, 16, 32, 64; 0 = the size rule); accumulate: d_q += the quotient"""
+    check(lib().h2g_debug_kate_division_dev(VP(d_a), n, p64(np.ascontiguousarray(b, dtype=np.uint64)), VP(d_q),
+                                            int(bool(accumulate)), tile_s, VP(stream) if stream else None))
+
+
+def debug_kate_tile_s(n):
+    """h2g_debug_kate_tile_s: the tile_s kate_division's size rule takes for n coefficients (host only)"""
+    s = I32(0)
+    check(lib().h2g_debug_kate_tile_s(n, ctypes.byref(s)))
+    return s.value
 
 
 def msm_segmented(bases, scalars, seg_off, index=None):
