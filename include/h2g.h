@@ -148,6 +148,35 @@ int h2g_extended_to_coeff_dev(uint64_t dom, const void* d_a, void* d_out, void* 
 /* divide_by_vanishing_poly (domain.rs:297-316): in place on 2^extended_k */
 int h2g_divide_by_vanishing_poly(uint64_t dom, uint64_t* a);
 int h2g_divide_by_vanishing_poly_dev(uint64_t dom, void* d_a, void* stream);
+/* test seam: which kernels a transform of 2^log_n points takes -- the plan every NTT launches
+ * from, as a function of the call's shape alone.  n_in: the inputs present (zero beyond);
+ * out_len: the outputs kept, 0 = all; count: transforms per launch (< 1 = 1; more than 8:
+ * H2G_ERR_ARG); in_twist: the sub-coset transform's fused input twist; cus: the compute units
+ * planned for, 0 = the current device's as the library sees it (256 without a device);
+ * epilogue_one: no constant is left for the last pass (lagrange_to_coeff, coeff_to_extended
+ * and coeff_to_subcoset above 2^10 points; extended_to_coeff's zeta powers always leave one).
+ * Host only: needs no h2g_init. */
+enum {
+  H2G_NTT_FIRST_ONE_BLOCK = 0, /* the whole transform in one block's LDS: log_n <= 10, passes == 1 */
+  H2G_NTT_FIRST_SPARSE = 1,    /* 8-point first pass of two inputs: lg[0] == 3, n_in <= 2^log_n / 4 */
+  H2G_NTT_FIRST_PLAIN = 2,
+  H2G_NTT_FIRST_TWISTED = 3    /* in_twist above 2^10 points */
+};
+typedef struct h2g_ntt_plan {
+  int32_t passes;      /* P */
+  int32_t lg[6];       /* bits of pass p < P (3..6, the last 6), 0 beyond */
+  int32_t first;       /* H2G_NTT_FIRST_* */
+  int32_t last_trunc;  /* last pass stores under y < out_len (out_len < 2^log_n); 0 when passes == 1 */
+  int32_t last_one;    /* last pass without its epilogue product; 0 when passes == 1 */
+  int32_t cus;         /* the compute units planned for */
+  uint32_t blocks;     /* blocks of 4 waves that cover a pass's 2^log_n / 512 wave items; 0 when passes == 1 */
+  uint32_t first_grid; /* grid.x of the first pass */
+  uint32_t pgrid[6];   /* grid.x of the persistent pass p, 0 < p < P - 1: min(blocks, 2 cus / count), at
+                          least 1; 0 elsewhere.  Its waves stride over the items: when pgrid does not
+                          divide blocks, some take one item more than others */
+} h2g_ntt_plan;
+int h2g_debug_ntt_plan(uint32_t log_n, uint64_t n_in, uint64_t out_len, int count, int in_twist, int cus,
+                       int epilogue_one, h2g_ntt_plan* plan);
 
 /* ---- Polynomial<F, B> arithmetic (halo2_backend/src/poly.rs:200-276) ---------
  * op: 0 add a+b, 1 sub a-b, 2 mul a*b, 3 scale a*c, 4 sub_const a-c, 5 add_const a+c,

@@ -489,6 +489,21 @@ CASES = [
 ]
 
 
+# Circuits whose h(X) splits unevenly (degree - 1 no power of two) at a multi-pass size: the
+# extended domain is 2^13 .. 2^16, so extended_to_coeff ends in the truncated last pass and keeps
+# 3/4, 6/8, 5/8, 7/8, 11/16 and 15/16 of it, where every case above with such a degree sits at
+# k <= 7 and is served by the one-block kernel.  Pinned valid by tests/test_generated_circuits_cpu.py,
+# compared on the device by tests/test_gpu_generated_large.py.
+LARGE_CASES = [
+    dict(seed=701, k=11, degree=4),
+    dict(seed=702, k=11, degree=7, lookups=(1,), shuffle=True),
+    dict(seed=703, k=12, degree=6),
+    dict(seed=704, k=11, degree=8),
+    dict(seed=705, k=11, degree=12, gates=1),
+    dict(seed=706, k=12, degree=16, gates=1),
+]
+
+
 def case_id(case):
     return "-".join(f"{k[0]}{v}" if k in ("seed", "k", "degree") else k for k, v in case.items()
                     if k in ("seed", "k", "degree") or (k == "challenges" and v))

@@ -173,6 +173,30 @@ def test_the_list_covers_every_shape():
     assert not missing, missing
 
 
+# ----------------------------------------------------------------------------- the large cases
+@pytest.mark.parametrize("i", range(len(G.LARGE_CASES)), ids=[G.case_id(c) for c in G.LARGE_CASES])
+def test_large_case_is_valid(i):
+    """G.LARGE_CASES: one phase, satisfied, deterministic, and an extended domain above 2^10 of
+    which h(X) fills a part that is no power of two"""
+    circ, wit, fill = G.generate(**G.LARGE_CASES[i])
+    assert fill is None
+    d = circ.degree()
+    ek = circ.k + (d - 2).bit_length()
+    assert d == G.LARGE_CASES[i]["degree"] and 13 <= ek <= 16
+    assert (d - 1) & (d - 2) and (d - 1) << circ.k < 1 << ek
+    assert CR.check(circ, wit, []) == set()
+    assert _same((circ, wit, None), G.generate(**G.LARGE_CASES[i]))
+
+
+def test_the_large_list_splits_h_unevenly_at_every_extension():
+    assert len({c["seed"] for c in G.LARGE_CASES + G.CASES}) == len(G.LARGE_CASES) + len(G.CASES)
+    kept = set()
+    for c in G.LARGE_CASES:
+        e = (c["degree"] - 2).bit_length()
+        kept.add((c["degree"] - 1, 1 << e))
+    assert kept == {(3, 4), (6, 8), (5, 8), (7, 8), (11, 16), (15, 16)}
+
+
 # ----------------------------------------------------------------------------- refused proofs
 @pytest.mark.parametrize("make", [G.zero_table_lookup, G.unblinded_boolean], ids=lambda f: f.__name__)
 def test_oracle_refuses_an_identity_commitment(make):

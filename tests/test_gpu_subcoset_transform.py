@@ -6,9 +6,10 @@ test_gpu_parity / the golden fixtures): row t + 2^e m of the extended coset is t
 zeta w_ext^t w^m.  Outputs are compared as bytes -- fully reduced limbs, not values mod r.
 
 Sizes: k = 6 and 10 are the one-block kernel and its upper edge; k = 11 two passes with the
-short (5-bit) pass first; k = 13 the borrowed-bits split 3 + 4 + 6; k = 18 three 6-bit
-passes with the persistent middle pass.  Extended domains 2n and 16n at k = 6, 10, 13 and 4n
-at k = 11 and 18; every t of each.
+short (5-bit) pass first; k = 13 the borrowed-bits split 3 + 4 + 6; k = 16 the split
+4 + 6 + 6 (the twisted first pass of 4 bits); k = 18 three 6-bit passes with the persistent
+middle pass.  Extended domains 2n and 16n at k = 6, 10, 13 and 4n at k = 11, 16 and 18; every t
+of each.
 """
 import numpy as np
 import pytest
@@ -24,7 +25,8 @@ R_MINUS_1 = np.array([0x43e1f593f0000000, 0x2833e84879b97091, 0xb85045b68181585d
 ERR_ARG = 1  # H2G_ERR_ARG
 
 # (k, j): extended_k - k = ceil(log2(j - 1))
-CASES = [(6, 3), (6, 17), (10, 3), (10, 17), (11, 5), (13, 3), (13, 17), (18, 5)]
+# (16, 4): the twisted first pass at lg[0] == 4 (the split 4 + 6 + 6), a 4n extension of three pieces
+CASES = [(6, 3), (6, 17), (10, 3), (10, 17), (11, 5), (13, 3), (13, 17), (18, 5), (16, 4)]
 
 
 @pytest.fixture(scope="module", autouse=True)

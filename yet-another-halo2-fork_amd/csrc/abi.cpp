@@ -855,6 +855,35 @@ int h2g_divide_by_vanishing_poly_dev(uint64_t dom, void* a, void* stream) {
   return H2G_OK;
 }
 
+// test seam: ntt_plan, the function ntt_run launches from (host only, no device state)
+int h2g_debug_ntt_plan(uint32_t log_n, uint64_t n_in, uint64_t out_len, int count, int in_twist, int cus,
+                       int epilogue_one, h2g_ntt_plan* plan) {
+  static_assert(NTT_MAX_PASSES == 6 && (int)NTT_FIRST_ONE_BLOCK == H2G_NTT_FIRST_ONE_BLOCK &&
+                    (int)NTT_FIRST_SPARSE == H2G_NTT_FIRST_SPARSE && (int)NTT_FIRST_PLAIN == H2G_NTT_FIRST_PLAIN &&
+                    (int)NTT_FIRST_TWISTED == H2G_NTT_FIRST_TWISTED,
+                "h2g_ntt_plan mirrors NttPlan");
+  if (!plan) return fail(H2G_ERR_ARG, "debug_ntt_plan: null argument");
+  if (cus < 0) return fail(H2G_ERR_ARG, "debug_ntt_plan: negative cus");
+  if (log_n > FR_S) return fail(H2G_ERR_ARG, "debug_ntt_plan: log_n > S");
+  if (out_len > (1ull << log_n)) return fail(H2G_ERR_ARG, "debug_ntt_plan: out_len > 2^log_n");
+  const int ncu = cus ? cus : ntt_cus();
+  NttPlan pl;
+  if (!ntt_plan((int)log_n, n_in, out_len, count, in_twist, ncu, epilogue_one != 0, &pl))
+    return fail(H2G_ERR_ARG, "debug_ntt_plan: a shape the NTT refuses");
+  h2g_ntt_plan o = {};
+  o.passes = pl.lg.p;
+  for (int p = 0; p < pl.lg.p && p < 6; p++) o.lg[p] = pl.lg.lg[p];
+  o.first = pl.first;
+  o.last_trunc = pl.trunc;
+  o.last_one = pl.one;
+  o.cus = ncu;
+  o.blocks = pl.blocks;
+  o.first_grid = pl.first_grid;
+  for (int p = 0; p < 6; p++) o.pgrid[p] = pl.pgrid[p];
+  *plan = o;
+  return H2G_OK;
+}
+
 // host-pointer domain wrappers
 int h2g_lagrange_to_coeff(uint64_t dom, uint64_t* a) {
   NEED_DEV();

@@ -78,6 +78,34 @@ struct NttArgs {
   uint64_t tw_mul = 0, tw_mask = 0;
 };
 
+// Every choice ntt_run makes for one call, as a pure host function of the call's shape (test
+// seam: h2g_debug_ntt_plan, tests/test_ntt_plan_cpu.py).  ntt_run launches from this and
+// decides nothing itself, so a test that asks for a shape's plan knows which kernels ran.
+enum NttFirst {
+  NTT_FIRST_ONE_BLOCK = 0,  // ntt_small_kernel: the whole transform, P == 1 (twisted or not)
+  NTT_FIRST_SPARSE = 1,     // ntt_first_sparse29_kernel: lg[0] == 3 and n_in <= N / 4
+  NTT_FIRST_PLAIN = 2,      // ntt_pass29_kernel<M, false>
+  NTT_FIRST_TWISTED = 3,    // ntt_pass29_kernel<M, true> (in_twist; never the sparse kernel)
+};
+struct NttPlan {
+  NttPlanLg lg;          // P and the bits of every pass
+  int batch = 1;         // transforms per launch (grid.y; grid.x of the one-block kernel)
+  int first = NTT_FIRST_ONE_BLOCK;
+  uint64_t items = 0;    // wave items of a pass per transform: N / 512 whatever the pass's bits
+  unsigned blocks = 0;   // grid.x of the plain / twisted first pass and of the last pass
+  unsigned first_grid = 0;  // grid.x of the first pass: `batch`, N / 8 / 256 (sparse) or `blocks`
+  // grid.x of the persistent middle pass p, 0 < p < P - 1: min(blocks, 2 cus / batch), >= 1;
+  // 0 elsewhere.  A wave walks item, item + 4 grid, ...: ragged when grid does not divide blocks.
+  unsigned pgrid[NTT_MAX_PASSES] = {0, 0, 0, 0, 0, 0};
+  bool trunc = false;    // last pass: out_len < N, predicated stores
+  bool one = false;      // last pass: no epilogue product
+};
+// out_len 0 = N; count < 1 = 1; epilogue_one: the per-(y mod 3) epilogue constants are all
+// one.  false: a shape ntt_run refuses (count > NTT_MAX_BATCH, L outside 0..28).
+bool ntt_plan(int L, uint64_t n_in, uint64_t out_len, int count, int in_twist, int cus, bool epilogue_one,
+              NttPlan* out);
+int ntt_cus();  // the CU count ntt_run plans with: the current device's, 256 when it has none
+
 void ntt_split(int L, int* P, int lg[NTT_MAX_PASSES]);
 hipError_t ntt_build_tables(NttTables* t, const Fr& omega, int L, hipStream_t st, const Fr& fold = Fr::one());
 void ntt_free_tables(NttTables* t);

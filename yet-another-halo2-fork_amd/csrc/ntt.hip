@@ -368,7 +368,7 @@ ntt_first_sparse29_kernel(Fr* data, NttIo io, uint64_t n_in, NttTables tab, cons
   });
 }
 
-static int ntt_cus() {
+int ntt_cus() {
   static int cus = 0;
   if (!cus) {
     int dev = 0;
@@ -635,37 +635,80 @@ hipError_t ntt_init_attributes() {
                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
 
+// ntt_run's decisions (ntt.h NttPlan).  Every pass has N / 512 wave items per transform: a
+// wave owns CPW = 64 / 2^(M-3) columns of 2^M points.
+static_assert(8 * WaveDif29<3>::CPW == 512 && 16 * WaveDif29<4>::CPW == 512 && 32 * WaveDif29<5>::CPW == 512 &&
+                  64 * WaveDif29<6>::CPW == 512,
+              "a wave item is 512 elements");
+
+bool ntt_plan(int L, uint64_t n_in, uint64_t out_len, int count, int in_twist, int cus, bool epilogue_one,
+              NttPlan* out) {
+  NttPlan pl;
+  if (L < 0 || L > 28 || !out) return false;
+  const uint64_t N = 1ull << L;
+  const int B = count < 1 ? 1 : count;
+  if (B > NTT_MAX_BATCH) return false;
+  pl.batch = B;
+  ntt_split(L, &pl.lg.p, pl.lg.lg);
+  const int P = pl.lg.p;
+  const int* lg = pl.lg.lg;
+  if (P == 1) {
+    pl.first = NTT_FIRST_ONE_BLOCK;
+    pl.first_grid = (unsigned)B;
+    *out = pl;
+    return true;
+  }
+  if (P > NTT_MAX_PASSES || lg[P - 1] != 6) return false;
+  for (int p = 0; p < P; p++)
+    if (lg[p] < 3 || lg[p] > 6) return false;
+  pl.items = N / 512;
+  pl.blocks = (unsigned)((pl.items + NTT_WAVES - 1) / NTT_WAVES);
+  if (in_twist) {
+    pl.first = NTT_FIRST_TWISTED;
+    pl.first_grid = pl.blocks;
+  } else if (lg[0] == 3 && n_in <= (N >> 2)) {
+    pl.first = NTT_FIRST_SPARSE;
+    pl.first_grid = (unsigned)(((N >> 3) + NTT_THREADS - 1) / NTT_THREADS);
+  } else {
+    pl.first = NTT_FIRST_PLAIN;
+    pl.first_grid = pl.blocks;
+  }
+  // the passes after the first: two 4-wave blocks per CU over the whole batch, every wave several groups
+  const uint64_t want = (uint64_t)(cus > 0 ? cus : 0) * 2 / (uint64_t)B;
+  const unsigned pb = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(pl.blocks, want));
+  for (int p = 1; p < P - 1; p++) pl.pgrid[p] = pb;
+  pl.trunc = (out_len ? out_len : N) < N;
+  pl.one = epilogue_one;
+  *out = pl;
+  return true;
+}
+
 // the twisted first pass: never the sparse kernel (n_in = N), never a later pass
 template <int M>
-static void launch_pass_tw(const NttArgs& a, const NttIo& io, int B, int L, const NttConst29& k29,
+static void launch_pass_tw(const NttArgs& a, const NttIo& io, const NttPlan& pl, int L, const NttConst29& k29,
                            const NttTwist29& tw, hipStream_t st) {
-  const uint64_t waves = (1ull << L) / ((1ull << M) * WaveDif29<M>::CPW);
-  const unsigned blocks = (unsigned)((waves + NTT_WAVES - 1) / NTT_WAVES);
-  hipLaunchKernelGGL((ntt_pass29_kernel<M, true>), dim3(blocks, (unsigned)B), dim3(NTT_THREADS), 0, st, a.work, io, 1,
-                     a.n_in, a.tab, (const Fr*)(a.tab.pass_tw + a.tab.pass_off[0]), L, L, 1, k29, tw);
+  hipLaunchKernelGGL((ntt_pass29_kernel<M, true>), dim3(pl.first_grid, (unsigned)pl.batch), dim3(NTT_THREADS), 0, st,
+                     a.work, io, 1, a.n_in, a.tab, (const Fr*)(a.tab.pass_tw + a.tab.pass_off[0]), L, L, 1, k29, tw);
 }
 
 template <int M>
-static void launch_pass(const NttArgs& a, const NttIo& io, int B, int p, int first, uint64_t n_in, int L, int lrem,
-                        int dist, const NttConst29& k29, hipStream_t st) {
-  const uint64_t N = 1ull << L;
-  const uint64_t waves = N / ((1ull << M) * WaveDif29<M>::CPW);
-  const unsigned blocks = (unsigned)((waves + NTT_WAVES - 1) / NTT_WAVES);
-  if (M == 3 && first && n_in <= (N >> 2)) {
-    const uint64_t S = N >> 3;
-    hipLaunchKernelGGL(ntt_first_sparse29_kernel, dim3((unsigned)((S + NTT_THREADS - 1) / NTT_THREADS), (unsigned)B),
-                       dim3(NTT_THREADS), 0, st, a.work, io, n_in, a.tab,
-                       (const Fr*)(a.tab.pass_tw + a.tab.pass_off[p]), L, dist, k29);
+static void launch_pass(const NttArgs& a, const NttIo& io, const NttPlan& pl, int p, int L, int lrem,
+                        const NttConst29& k29, hipStream_t st) {
+  const int first = p == 0;
+  const uint64_t n_in = first ? a.n_in : 0;
+  const int dist = first ? a.in_distribute : 0;
+  const unsigned B = (unsigned)pl.batch;
+  if (first && pl.first == NTT_FIRST_SPARSE) {
+    hipLaunchKernelGGL(ntt_first_sparse29_kernel, dim3(pl.first_grid, B), dim3(NTT_THREADS), 0, st, a.work, io, n_in,
+                       a.tab, (const Fr*)(a.tab.pass_tw + a.tab.pass_off[p]), L, dist, k29);
     return;
   }
-  if (!first) {  // two 4-wave blocks per CU over the whole batch, every wave several groups
-    const uint64_t want = (uint64_t)ntt_cus() * 2 / (uint64_t)B;
-    const unsigned pb = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(blocks, want));
-    hipLaunchKernelGGL(ntt_pass29p_kernel<M>, dim3(pb, (unsigned)B), dim3(NTT_THREADS), 0, st, a.work, a.tab,
-                       (const Fr*)(a.tab.pass_tw + a.tab.pass_off[p]), L, lrem, waves);
+  if (!first) {
+    hipLaunchKernelGGL(ntt_pass29p_kernel<M>, dim3(pl.pgrid[p], B), dim3(NTT_THREADS), 0, st, a.work, a.tab,
+                       (const Fr*)(a.tab.pass_tw + a.tab.pass_off[p]), L, lrem, pl.items);
     return;
   }
-  hipLaunchKernelGGL((ntt_pass29_kernel<M, false>), dim3(blocks, (unsigned)B), dim3(NTT_THREADS), 0, st, a.work, io,
+  hipLaunchKernelGGL((ntt_pass29_kernel<M, false>), dim3(pl.first_grid, B), dim3(NTT_THREADS), 0, st, a.work, io,
                      first, n_in, a.tab, (const Fr*)(a.tab.pass_tw + a.tab.pass_off[p]), L, lrem, dist, k29,
                      NttNoTwist{});
 }
@@ -674,35 +717,6 @@ hipError_t ntt_run(const NttArgs& a, hipStream_t st) {
   const int L = a.tab.L;
   const uint64_t N = 1ull << L;
   const uint64_t out_len = a.out_len ? a.out_len : N;
-  const int B = a.count < 1 ? 1 : a.count;
-  if (B > NTT_MAX_BATCH) return hipErrorInvalidValue;
-  NttIo io = {};
-  for (int b = 0; b < B; b++) {
-    io.src[b] = B == 1 ? a.src : a.srcs[b];
-    io.dst[b] = B == 1 ? a.dst : a.dsts[b];
-  }
-  NttPlanLg plan;
-  ntt_split(L, &plan.p, plan.lg);
-  const int P = plan.p;
-  const int* lg = plan.lg;
-  if (a.in_twist && (!a.tw_lo || !a.tw_hi || a.n_in > N)) return hipErrorInvalidValue;
-  // gamma = zeta g, the twist's ratio (in_z1 = zeta)
-  const Fr gamma = a.in_twist ? a.tw_g * a.in_z1 : Fr::one();
-  if (P == 1 && a.in_twist) {
-    const size_t sm = (N + N / 2 + 1) * sizeof(Fr);
-    NttTwistFr tw = {a.tw_lo, a.tw_hi, a.tw_bits, a.tw_mul, a.tw_mask, pow_u64(gamma, 256)};
-    hipLaunchKernelGGL(ntt_small_kernel<true>, dim3((unsigned)B), dim3(256), sm, st, io, a.n_in, out_len, a.tab, L, 1,
-                       a.in_z1, a.in_z2, a.has_scale, a.scale, a.out_distribute, a.out_z1, a.out_z2, tw);
-    return hipGetLastError();
-  }
-  if (P == 1) {
-    const size_t sm = (N + N / 2 + 1) * sizeof(Fr);
-    hipLaunchKernelGGL(ntt_small_kernel<false>, dim3((unsigned)B), dim3(256), sm, st, io, a.n_in, out_len, a.tab, L,
-                       a.in_distribute, a.in_z1, a.in_z2, a.has_scale, a.scale, a.out_distribute, a.out_z1,
-                       a.out_z2, NttNoTwist{});
-    return hipGetLastError();
-  }
-  if (P > NTT_MAX_PASSES || lg[P - 1] != 6 || !a.tab.pass_tw) return hipErrorInvalidValue;
   // epilogue multiplier per (y mod 3): scale * zeta-power / the scale folded into the
   // first pass's table, on the host
   Fr mul[3];
@@ -714,6 +728,35 @@ hipError_t ntt_run(const NttArgs& a, hipStream_t st) {
     mul[r] = m;
     one = one && m == Fr::one();
   }
+  NttPlan pl;
+  if (!ntt_plan(L, a.n_in, a.out_len, a.count, a.in_twist, ntt_cus(), one, &pl)) return hipErrorInvalidValue;
+  const int B = pl.batch;
+  NttIo io = {};
+  for (int b = 0; b < B; b++) {
+    io.src[b] = B == 1 ? a.src : a.srcs[b];
+    io.dst[b] = B == 1 ? a.dst : a.dsts[b];
+  }
+  const NttPlanLg& plan = pl.lg;
+  const int P = plan.p;
+  const int* lg = plan.lg;
+  if (a.in_twist && (!a.tw_lo || !a.tw_hi || a.n_in > N)) return hipErrorInvalidValue;
+  // gamma = zeta g, the twist's ratio (in_z1 = zeta)
+  const Fr gamma = a.in_twist ? a.tw_g * a.in_z1 : Fr::one();
+  if (pl.first == NTT_FIRST_ONE_BLOCK && a.in_twist) {
+    const size_t sm = (N + N / 2 + 1) * sizeof(Fr);
+    NttTwistFr tw = {a.tw_lo, a.tw_hi, a.tw_bits, a.tw_mul, a.tw_mask, pow_u64(gamma, 256)};
+    hipLaunchKernelGGL(ntt_small_kernel<true>, dim3(pl.first_grid), dim3(256), sm, st, io, a.n_in, out_len, a.tab, L,
+                       1, a.in_z1, a.in_z2, a.has_scale, a.scale, a.out_distribute, a.out_z1, a.out_z2, tw);
+    return hipGetLastError();
+  }
+  if (pl.first == NTT_FIRST_ONE_BLOCK) {
+    const size_t sm = (N + N / 2 + 1) * sizeof(Fr);
+    hipLaunchKernelGGL(ntt_small_kernel<false>, dim3(pl.first_grid), dim3(256), sm, st, io, a.n_in, out_len, a.tab, L,
+                       a.in_distribute, a.in_z1, a.in_z2, a.has_scale, a.scale, a.out_distribute, a.out_z1,
+                       a.out_z2, NttNoTwist{});
+    return hipGetLastError();
+  }
+  if (!a.tab.pass_tw) return hipErrorInvalidValue;
   NttConst29 k29;  // the F29 passes' constants
   k29.z1 = storage_to_f29<FrParams>(a.in_z1);
   k29.z2 = storage_to_f29<FrParams>(a.in_z2);
@@ -723,43 +766,37 @@ hipError_t ntt_run(const NttArgs& a, hipStream_t st) {
   // last pass: work -> dst in natural order.
   int lrem = L;
   for (int p = 0; p < P - 1; p++) {
-    const int first = p == 0;
-    const uint64_t nin = first ? a.n_in : 0;
-    const int dist = first ? a.in_distribute : 0;
-    if (first && a.in_twist) {
+    if (p == 0 && pl.first == NTT_FIRST_TWISTED) {
       NttTwist29 tw = {a.tw_lo, a.tw_hi, a.tw_bits, a.tw_mul, a.tw_mask,
                        storage_to_f29<FrParams>(pow_u64(gamma, 1ull << (L - 3)))};
       switch (lg[0]) {
-        case 3: launch_pass_tw<3>(a, io, B, L, k29, tw, st); break;
-        case 4: launch_pass_tw<4>(a, io, B, L, k29, tw, st); break;
-        case 5: launch_pass_tw<5>(a, io, B, L, k29, tw, st); break;
-        case 6: launch_pass_tw<6>(a, io, B, L, k29, tw, st); break;
+        case 3: launch_pass_tw<3>(a, io, pl, L, k29, tw, st); break;
+        case 4: launch_pass_tw<4>(a, io, pl, L, k29, tw, st); break;
+        case 5: launch_pass_tw<5>(a, io, pl, L, k29, tw, st); break;
+        case 6: launch_pass_tw<6>(a, io, pl, L, k29, tw, st); break;
         default: return hipErrorInvalidValue;
       }
       lrem -= lg[0];
       continue;
     }
     switch (lg[p]) {
-      case 3: launch_pass<3>(a, io, B, p, first, nin, L, lrem, dist, k29, st); break;
-      case 4: launch_pass<4>(a, io, B, p, first, nin, L, lrem, dist, k29, st); break;
-      case 5: launch_pass<5>(a, io, B, p, first, nin, L, lrem, dist, k29, st); break;
-      case 6: launch_pass<6>(a, io, B, p, first, nin, L, lrem, dist, k29, st); break;
+      case 3: launch_pass<3>(a, io, pl, p, L, lrem, k29, st); break;
+      case 4: launch_pass<4>(a, io, pl, p, L, lrem, k29, st); break;
+      case 5: launch_pass<5>(a, io, pl, p, L, lrem, k29, st); break;
+      case 6: launch_pass<6>(a, io, pl, p, L, lrem, k29, st); break;
       default: return hipErrorInvalidValue;
     }
     lrem -= lg[p];
   }
   {
-    const uint64_t waves = N / (64ull * WaveDif29<6>::CPW);
-    const unsigned blocks = (unsigned)((waves + NTT_WAVES - 1) / NTT_WAVES);
-    const dim3 g(blocks, (unsigned)B), b(NTT_THREADS);
-    const bool tr = out_len < N;
-    if (tr && one)
+    const dim3 g(pl.blocks, (unsigned)B), b(NTT_THREADS);
+    if (pl.trunc && pl.one)
       hipLaunchKernelGGL((ntt_last29_kernel<true, true>), g, b, 0, st, (const Fr*)a.work, io, out_len, a.tab, L, plan,
                          k29);
-    else if (tr)
+    else if (pl.trunc)
       hipLaunchKernelGGL((ntt_last29_kernel<true, false>), g, b, 0, st, (const Fr*)a.work, io, out_len, a.tab, L,
                          plan, k29);
-    else if (one)
+    else if (pl.one)
       hipLaunchKernelGGL((ntt_last29_kernel<false, true>), g, b, 0, st, (const Fr*)a.work, io, out_len, a.tab, L,
                          plan, k29);
     else

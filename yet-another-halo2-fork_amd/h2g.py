@@ -65,6 +65,7 @@ _SIGS = {
     "h2g_extended_to_coeff_dev": ([U64, VP, VP, VP], I32),
     "h2g_divide_by_vanishing_poly": ([U64, U64P], I32),
     "h2g_divide_by_vanishing_poly_dev": ([U64, VP, VP], I32),
+    "h2g_debug_ntt_plan": ([U32, U64, U64, I32, I32, I32, I32, VP], I32),
     "h2g_fr_op": ([I32, U64P, U64P, U64P, U64P, SZ], I32),
     "h2g_fr_op_dev": ([I32, VP, VP, U64P, VP, SZ, VP], I32),
     "h2g_fr_batch_invert": ([U64P, SZ], I32),
@@ -453,6 +454,28 @@ class Domain:
         if self.h:
             lib().h2g_domain_free(self.h)
             self.h = 0
+
+
+NTT_FIRST = ("one_block", "sparse", "plain", "twisted")  # H2G_NTT_FIRST_*
+
+
+class NttPlan(ctypes.Structure):  # h2g_ntt_plan
+    _fields_ = [("passes", ctypes.c_int32), ("lg", ctypes.c_int32 * 6), ("first", ctypes.c_int32),
+                ("last_trunc", ctypes.c_int32), ("last_one", ctypes.c_int32), ("cus", ctypes.c_int32),
+                ("blocks", ctypes.c_uint32), ("first_grid", ctypes.c_uint32), ("pgrid", ctypes.c_uint32 * 6)]
+
+
+def debug_ntt_plan(log_n, n_in, out_len=0, count=1, in_twist=False, cus=256, epilogue_one=True):
+    """h2g_debug_ntt_plan (test seam, host only): the kernels a 2^log_n-point transform takes ->
+    dict(split, first, trunc, one, cus, blocks, first_grid, pgrid).  split: the bits of each pass;
+    first: one of NTT_FIRST; trunc / one: the last-pass variant (both False for a one-pass
+    transform); pgrid: {p: grid} of the persistent middle passes.  cus = 0: the current device's."""
+    pl = NttPlan()
+    check(lib().h2g_debug_ntt_plan(log_n, n_in, out_len, count, int(bool(in_twist)), cus, int(bool(epilogue_one)),
+                                   ctypes.byref(pl)))
+    return {"split": tuple(pl.lg[:pl.passes]), "first": NTT_FIRST[pl.first], "trunc": bool(pl.last_trunc),
+            "one": bool(pl.last_one), "cus": pl.cus, "blocks": pl.blocks, "first_grid": pl.first_grid,
+            "pgrid": {p: pl.pgrid[p] for p in range(1, pl.passes - 1)}}
 
 
 # ----------------------------------------------------------------- poly ops
