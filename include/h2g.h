@@ -194,6 +194,43 @@ int h2g_fr_prefix_product_dev(const void* d_a, void* d_out, size_t n, void* stre
  * of the lookup argument's sorts and compactions (lookup/prover.rs:410-494) */
 int h2g_u32_exclusive_scan_dev(const void* d_in, void* d_out, size_t n, void* stream);
 
+/* ---- a witness of Assigned<F> cells to field elements (csrc/assigned.hip) ------------
+ * batch_invert_assigned (halo2_frontend/src/circuit.rs:363-404), the last step of
+ * WitnessCalculator::calc: the frontend holds every advice cell as Zero, Trivial(x) or
+ * Rational(numerator, denominator) (halo2_frontend/src/plonk/assigned.rs), inverts the
+ * Rational cells' denominators in one batch and multiplies (Assigned::evaluate,
+ * assigned.rs:352-364).  The wire form is what one walk over Vec<Vec<Assigned<F>>> emits:
+ *   num   : ncells Fr, Assigned::numerator() of every cell (0 for Zero)
+ *   index : nden flat cell indices into num, one per Rational cell, strictly increasing
+ *   den   : nden Fr, that cell's denominator
+ * out[index[j]] = num[index[j]] * den[j]^-1, and 0 where den[j] == 0 (ff::BatchInvert skips
+ * zeros; x / 0 = 0 as in assigned.rs:280-295); a denominator of 1 is inverted like any other.
+ * Every cell that is not listed: out = num.  out == num (in place) touches only the listed
+ * cells, so its cost follows nden, not ncells.  den is not modified.  nden == 0 is a copy
+ * (nothing in place), ncells == 0 is H2G_OK.  Field inverses are unique: the result is the
+ * reference's for every input.
+ * Host entry: validates before it touches the device -- a missing pointer, an index >=
+ * ncells or a list that is not strictly increasing is H2G_ERR_ARG, the message names the
+ * entry, out is left as it was -- then copies in and out and returns with the result.
+ * _dev: device pointers, 16-byte aligned (H2G_ERR_ARG otherwise); asynchronous on `stream`
+ * like h2g_fr_batch_invert_dev, with nden Fr of scratch from the device workspace
+ * (H2G_ERR_NOMEM, nothing left allocated, if that cannot grow).  The index contract is the
+ * caller's: an index >= ncells is skipped and never dereferenced, a repeated index leaves that
+ * cell with an unspecified value.  Elements are reduced Montgomery limbs, as everywhere.
+ * The inverses are never stored: the inversion's backward pass, which holds den[j]^-1 in
+ * registers, loads index[j] and num[index[j]] and stores out[index[j]]. */
+int h2g_assigned_to_fr(const uint64_t* num, size_t ncells, const uint64_t* index, const uint64_t* den, size_t nden,
+                       uint64_t* out);
+int h2g_assigned_to_fr_dev(const void* d_num, size_t ncells, const void* d_index, const void* d_den, size_t nden,
+                           void* d_out, void* stream);
+/* test seams (tests/test_gpu_assigned.py).  h2g_debug_assigned_per: the denominators per
+ * first-level thread the size rule takes for nden of them (2, 4, 8 or 16; host only: needs no
+ * h2g_init).  h2g_debug_assigned_to_fr_dev: h2g_assigned_to_fr_dev with that many at any nden;
+ * per = 0 is the rule, a value that is none of those H2G_ERR_ARG. */
+int h2g_debug_assigned_per(size_t nden, int* per);
+int h2g_debug_assigned_to_fr_dev(const void* d_num, size_t ncells, const void* d_index, const void* d_den,
+                                 size_t nden, void* d_out, int per, void* stream);
+
 /* ---- device memory / stream helpers --------------------------------------- */
 int h2g_dev_alloc(size_t bytes, void** d_ptr);
 int h2g_dev_free(void* d_ptr);
@@ -457,6 +494,30 @@ typedef struct {
 } h2g_prove_inputs;
 int h2g_create_proof_multi(uint64_t params, uint64_t pk, const h2g_prove_inputs* in, uint8_t* proof,
                            size_t proof_cap, size_t* proof_len);
+/* h2g_create_proof_multi with the witness as the frontend holds it (Assigned<F> cells, the
+ * wire form of h2g_assigned_to_fr): batch_invert_assigned (circuit.rs:363-404) runs on the
+ * device, not in the caller's WitnessCalculator::calc.  in->advice and in->witness must both
+ * be NULL (H2G_ERR_ARG otherwise); everything else in h2g_prove_inputs keeps its meaning.
+ * fill is h2g_witness_source_multi.fill that writes phase p's NUMERATORS into `advice` (the
+ * key's host staging) and points *dens at this (circuit, phase)'s Rational cells: flat
+ * indices into `advice` (column * n + row), strictly increasing, and their denominators --
+ * memory the callback owns, valid until the next fill call or the return of the proof.
+ * count == 0 (index / den may be NULL) is a witness without divisions.  Entries that name
+ * cells outside phase p's columns are ignored.  An index >= num_advice * n, or a list that is
+ * not strictly increasing, fails the proof with H2G_ERR_ARG (the message names the circuit and
+ * the phase).  The proof is h2g_create_proof_multi's for the evaluated advice, byte for byte.
+ * The phase's columns and the list go up to a scratch the key owns (num_advice x n Fr, counted
+ * by h2g_pk_memory, released by h2g_pk_free), are converted there in place on the prover's
+ * stream, and enter the prover as device advice.  Under a shard or SPMD transport every rank's
+ * callback supplies the same witness, as with h2g_witness_source. */
+typedef struct { const uint64_t* index; const uint64_t* den; size_t count; } h2g_assigned_dens;
+typedef struct {
+  void* ctx;
+  int (*fill)(void* ctx, uint32_t circuit, uint32_t phase, const uint64_t* challenges, uint64_t* advice,
+              h2g_assigned_dens* dens);
+} h2g_assigned_source;
+int h2g_create_proof_assigned(uint64_t params, uint64_t pk, const h2g_prove_inputs* in,
+                              const h2g_assigned_source* source, uint8_t* proof, size_t proof_cap, size_t* proof_len);
 /* a native ChaCha20Rng::from_seed(seed) (rand_chacha 0.3) as an h2g_rng: *out's callbacks
  * draw from it (the RngCore a Rust host passes to create_proof, without the host); the
  * proof equals the rng_seed path's bytes.  h2g_rng_free releases it. */

@@ -796,7 +796,8 @@ int h2g_pk_memory(uint64_t pk_h, uint64_t out[4]) {
            p.lkb_canon.len * sizeof(CanonKey) + (p.lkb_key[0].len + p.lkb_key[1].len) * sizeof(uint64_t) +
            (p.lkb_idx[0].len + p.lkb_idx[1].len) * sizeof(uint32_t) + p.lkb_scr.len +
            (p.slab_buf.len + p.x_send.len + p.x_recv.len + p.blind_d.len) * sizeof(Fr) +
-           p.d_segs.len * sizeof(CopySeg) + p.d_seeds.len * sizeof(uint32_t) + p.d_offsets.len * sizeof(uint64_t);
+           p.d_segs.len * sizeof(CopySeg) + p.d_seeds.len * sizeof(uint32_t) + p.d_offsets.len * sizeof(uint64_t) +
+           (p.asg_num.len + p.asg_den.len) * sizeof(Fr) + p.asg_idx.len * sizeof(uint64_t);
   uint64_t ext_arrays = 2 + (p.h_gather ? 1 : 0);  // h_ext, h_coeff, h_gather
   if (!p.cosets) {
     const uint64_t per_ws = (uint64_t)p.cs.A + p.cs.I + p.cs.nsets + 3 * (uint64_t)p.cs.NL + p.cs.NS;

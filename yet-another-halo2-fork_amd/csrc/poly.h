@@ -23,6 +23,9 @@ hipError_t poly_batch_invert(Fr* a, size_t n, Fr* scratch, hipStream_t st);
 // POLY_INV_MAX_BATCH arrays per launch
 static constexpr int POLY_INV_MAX_BATCH = 16;
 hipError_t poly_batch_invert_multi(Fr* const* a, Fr* const* scratch, int count, size_t n, hipStream_t st);
+// the batch inversion's middle level on its own (inv_regs_kernel): a[0..m) in place, zeros
+// stay zero, one field inversion per 16 elements, no scratch (assigned.hip)
+hipError_t poly_inv_regs(Fr* a, size_t m, hipStream_t st);
 // out[i] = prod_{j<=i} a[j]; scratch >= 2 * ceil(n / 2^?) Fr (see poly.hip)
 hipError_t poly_prefix_product(const Fr* a, Fr* out, size_t n, Fr* scratch, size_t scratch_len, hipStream_t st);
 size_t poly_prefix_scratch_len(size_t n);

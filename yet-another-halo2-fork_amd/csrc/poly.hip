@@ -175,6 +175,15 @@ hipError_t poly_batch_invert_multi(Fr* const* a, Fr* const* scratch, int count, 
   return hipGetLastError();
 }
 
+hipError_t poly_inv_regs(Fr* a, size_t m, hipStream_t st) {
+  if (m == 0) return hipSuccess;
+  InvBatch bt = {};
+  bt.pref[0] = a;
+  const size_t T2 = (m + INV_REG - 1) / INV_REG;
+  hipLaunchKernelGGL(inv_regs_kernel, dim3((unsigned)((T2 + PT - 1) / PT), 1), dim3(PT), 0, st, bt, m);
+  return hipGetLastError();
+}
+
 hipError_t poly_batch_invert(Fr* a, size_t n, Fr* scratch, hipStream_t st) {
   return poly_batch_invert_multi(&a, &scratch, 1, n, st);
 }

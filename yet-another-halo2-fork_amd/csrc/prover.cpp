@@ -14,6 +14,7 @@
 // and O(#queries^2) interpolation; every length-n or extended-length operation is a
 // kernel (MSM, NTT, prover_kernels.hip, poly.hip).  MSM results come back to the host
 // (they enter the transcript), which is the only per-step synchronisation.
+#include "assigned.h"
 #include "multiopen.h"
 
 using namespace h2g;
@@ -122,6 +123,7 @@ struct ProveIn {
   bool adv_dev = false;
   const h2g_witness_source* src1 = nullptr;       // one circuit's per-phase witness source
   const h2g_witness_source_multi* src = nullptr;  // per-circuit per-phase witness source
+  const h2g_assigned_source* asg = nullptr;       // the same, as Assigned cells (h2g_create_proof_assigned)
   const uint64_t* const* instance = nullptr;      // [nc] num_instance x n Fr (zero padded)
   const uint32_t* const* inst_lens = nullptr;     // [nc] num_instance lengths
   ProverRng* rng = nullptr;
@@ -261,13 +263,68 @@ struct ProofRun {
     for (const G1Affine& cm : cms) RCCHK(write_point(cm));
     return H2G_OK;
   }
+  // h2g_create_proof_assigned: circuit ci's phase-ph numerators (w.wit_pin) and its Rational
+  // cells go up to the key's scratch and are evaluated there in place on the prover's stream
+  // (assigned.hip); the phase then reads the scratch as device advice
+  int assigned_convert(int ci, int ph, const std::vector<int>& cols, CircuitWs& w, const h2g_assigned_dens& dn) {
+    const size_t cells = (size_t)pk.cs.A * n;
+    const std::string at = "circuit " + std::to_string(ci) + " phase " + std::to_string(ph);
+    if (dn.count && (!dn.index || !dn.den))
+      return fail(H2G_ERR_ARG, "create_proof_assigned: null denominator list at " + at);
+    bool inside = true;  // every entry in one of this phase's columns (the usual case: no copy)
+    for (size_t j = 0; j < dn.count; j++) {
+      const uint64_t c = dn.index[j];
+      if (c >= cells)
+        return fail(H2G_ERR_ARG, "create_proof_assigned: index[" + std::to_string(j) + "] = " + std::to_string(c) +
+                                     " is not below num_advice * n at " + at);
+      if (j && c <= dn.index[j - 1])
+        return fail(H2G_ERR_ARG, "create_proof_assigned: index[" + std::to_string(j) +
+                                     "] does not exceed the entry before it (the list must be strictly increasing) at " + at);
+      inside = inside && pk.cs.adv_phase[c >> pk.cs.k] == ph;  // n = 2^k
+    }
+    const uint64_t* idx = dn.index;
+    const uint64_t* den = dn.den;
+    size_t m = dn.count;
+    if (!inside) {
+      asg_idx_h.clear();
+      asg_den_h.clear();
+      for (size_t j = 0; j < dn.count; j++)
+        if (pk.cs.adv_phase[dn.index[j] >> pk.cs.k] == ph) {
+          asg_idx_h.push_back(dn.index[j]);
+          asg_den_h.push_back(fr_from_limbs(dn.den + 4 * j));
+        }
+      idx = asg_idx_h.data();
+      den = reinterpret_cast<const uint64_t*>(asg_den_h.data());
+      m = asg_idx_h.size();
+    }
+    HIPCHK(pk.asg_num.ensure(cells));  // sizes first, then pointers (DevArr)
+    HIPCHK(pk.asg_idx.ensure(m));
+    HIPCHK(pk.asg_den.ensure(m));
+    if (m) HIPCHK(d->work.ensure(m * sizeof(Fr) + 32));
+    for (int c : cols)
+      HIPCHK(hipMemcpyAsync(pk.asg_num.p + n * c, w.wit_pin + 4 * n * c, n * sizeof(Fr), hipMemcpyHostToDevice, st));
+    if (m == 0) return H2G_OK;
+    HIPCHK(hipMemcpyAsync(pk.asg_idx.p, idx, m * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(pk.asg_den.p, den, m * sizeof(Fr), hipMemcpyHostToDevice, st));
+    HIPCHK(pk.asg_ev.ensure());
+    HIPCHK(hipEventRecord(pk.asg_ev, st));
+    asg_pending = true;
+    HIPCHK(assigned_to_fr(pk.asg_num.p, cells, pk.asg_idx.p, pk.asg_den.p, m, pk.asg_num.p, d->work.as<Fr>(), 0, st));
+    return H2G_OK;
+  }
   int rng_ok() { return rng.failed() ? fail(H2G_ERR_ARG, "create_proof: the caller's RNG failed") : H2G_OK; }
 
   const size_t unusable = n - (size_t)(bf + 1);
   // host staging that device copies read asynchronously: lives until the proof returns
   // (every copy has completed by then: the final commitment is collected after it)
   std::vector<Fr> adv_blind = std::vector<Fr>((size_t)ncirc * pk.cs.A * (bf + 1));
-  const bool from_src = in.src || in.src1;
+  const bool from_src = in.src || in.src1 || in.asg;
+  // h2g_create_proof_assigned: a list with cells outside its phase's columns, compacted to
+  // those inside (staging that asynchronous copies read, like adv_blind), and whether the
+  // last list's upload (the callback's memory until its next call) is still to be waited for
+  std::vector<uint64_t> asg_idx_h;
+  std::vector<Fr> asg_den_h;
+  bool asg_pending = false;
   const int NCH = (int)pk.cs.ch_phase.size();
   std::vector<Fr> challenges = std::vector<Fr>(NCH);
   StreamSyncGuard adv_guard{st};
@@ -499,14 +556,25 @@ int ProofRun::advice_phases() {
         for (int c : cols)
           if (pk.unblinded[c]) std::memset(w.wit_pin + 4 * (n * c + unusable), 0, (n - unusable) * sizeof(Fr));
         const uint64_t* chp = reinterpret_cast<const uint64_t*>(challenges.data());
-        const int frc = in.src ? in.src->fill(in.src->ctx, (uint32_t)ci, (uint32_t)ph, chp, w.wit_pin)
-                               : in.src1->fill(in.src1->ctx, (uint32_t)ph, chp, w.wit_pin);
+        h2g_assigned_dens dn = {nullptr, nullptr, 0};
+        if (asg_pending) {  // the last list is the callback's again once its upload has been read
+          HIPCHK(hipEventSynchronize(pk.asg_ev));
+          asg_pending = false;
+        }
+        const int frc = in.asg   ? in.asg->fill(in.asg->ctx, (uint32_t)ci, (uint32_t)ph, chp, w.wit_pin, &dn)
+                        : in.src ? in.src->fill(in.src->ctx, (uint32_t)ci, (uint32_t)ph, chp, w.wit_pin)
+                                 : in.src1->fill(in.src1->ctx, (uint32_t)ph, chp, w.wit_pin);
         if (frc)
           return fail(H2G_ERR_ARG, "create_proof: witness source failed at " +
                                        (ncirc > 1 ? "circuit " + std::to_string(ci) + " " : std::string()) + "phase " +
                                        std::to_string(ph));
         from = w.wit_pin;
         from_dev = false;
+        if (in.asg) {
+          RCCHK(assigned_convert(ci, ph, cols, w, dn));
+          from = reinterpret_cast<const uint64_t*>(pk.asg_num.p);
+          from_dev = true;
+        }
       }
       // column by column: upload, blinding rows, and (when the MSMs go one by one) the
       // commitment at once, so that a column's MSM overlaps the next column's upload
@@ -1718,7 +1786,7 @@ int create_proof_entry(Device* d, uint64_t params, uint64_t pk, ProveIn& in, uin
   if (K.device != d->id) return fail(H2G_ERR_ARG, "create_proof: pk lives on another device");
   if (!proof_len || in.nc < 1 || in.nc > 1024) return fail(H2G_ERR_ARG, "create_proof: bad arguments");
   for (int c = 0; c < in.nc; c++) {
-    if (K.cs.A && !in.src && !in.src1 && (!in.advice || !in.advice[c])) return fail(H2G_ERR_ARG, "create_proof: null advice");
+    if (K.cs.A && !in.src && !in.src1 && !in.asg && (!in.advice || !in.advice[c])) return fail(H2G_ERR_ARG, "create_proof: null advice");
     if (K.cs.I && (!in.instance || !in.inst_lens || !in.instance[c] || !in.inst_lens[c]))
       return fail(H2G_ERR_ARG, "create_proof: null instance");  // InvalidInstances
   }
@@ -1786,6 +1854,27 @@ int h2g_create_proof_multi(uint64_t params, uint64_t pk, const h2g_prove_inputs*
   in.advice = p->advice;
   in.adv_dev = p->advice_on_device != 0;
   in.src = p->witness;
+  in.instance = p->instance;
+  in.inst_lens = p->instance_lens;
+  in.rng = rng.get();
+  in.vthreads = p->vanishing_threads;
+  return create_proof_entry(d, params, pk, in, proof, proof_cap, proof_len);
+}
+
+int h2g_create_proof_assigned(uint64_t params, uint64_t pk, const h2g_prove_inputs* p,
+                              const h2g_assigned_source* source, uint8_t* proof, size_t proof_cap, size_t* proof_len) {
+  NEED_DEV_P();
+  if (!p || p->num_circuits < 1) return fail(H2G_ERR_ARG, "create_proof: no circuits");
+  if (!source || !source->fill) return fail(H2G_ERR_ARG, "create_proof_assigned: null source");
+  if (p->advice || p->witness)
+    return fail(H2G_ERR_ARG, "create_proof_assigned: the witness comes from `source`; advice and witness must be NULL");
+  if (!p->rng && !p->rng_seed) return fail(H2G_ERR_ARG, "create_proof: neither an rng nor a seed");
+  if (p->rng && !p->rng->fill_bytes) return fail(H2G_ERR_ARG, "create_proof: the caller's rng needs fill_bytes");
+  std::unique_ptr<ProverRng> rng = p->rng ? std::make_unique<ProverRng>(p->rng->fill_bytes, p->rng->random_fr, p->rng->ctx)
+                                          : std::make_unique<ProverRng>(p->rng_seed);
+  ProveIn in;
+  in.nc = (int)std::min<uint32_t>(p->num_circuits, 1u << 20);
+  in.asg = source;
   in.instance = p->instance;
   in.inst_lens = p->instance_lens;
   in.rng = rng.get();

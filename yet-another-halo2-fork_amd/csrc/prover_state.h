@@ -208,6 +208,7 @@ struct ProvingKey {
   DevArr<unsigned long long> wsum_d;
   PinArr<unsigned long long> wsum_h;
   Event wsum_ev;
+  Event asg_ev;  // h2g_create_proof_assigned: the denominator list's upload has been read
   // pinned staging of a proof's small host-to-device uploads (blinding rows, seeds, staged
   // scalars; pk_upload): from pageable memory a hipMemcpyAsync costs 8-60 us of host time
   // (a staged copy), which left the GPU idle between the keccak-style circuit's 32 advice
@@ -303,6 +304,10 @@ struct ProvingKey {
   size_t xp_used = 0;
   // a stage's blinding rows, uploaded in one copy (upload_rows_batch)
   DevArr<Fr> blind_d;
+  // h2g_create_proof_assigned's scratch: the phase's numerators (num_advice x n, evaluated
+  // in place and read as device advice) and its Rational cells' indices and denominators
+  DevArr<Fr> asg_num, asg_den;
+  DevArr<uint64_t> asg_idx;
   DevArr<uint32_t> d_seeds;  // the vanishing argument's chunk seeds (8 words each) and offsets
   DevArr<uint64_t> d_offsets;
   // the keystream position of the vanishing argument's seed draws in the last proof with

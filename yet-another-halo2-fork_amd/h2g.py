@@ -186,6 +186,11 @@ _SIGS = {
     "h2g_pairing_check_batch_dev": ([VP, VP, SZ, VP, VP], I32),
     "h2g_verify_set_isolation": ([I32], I32),
     "h2g_debug_pairing_values": ([VP, U64P, SZ, U64P, U64P], I32),
+    "h2g_assigned_to_fr": ([U64P, SZ, U64P, U64P, SZ, U64P], I32),
+    "h2g_assigned_to_fr_dev": ([VP, SZ, VP, VP, SZ, VP, VP], I32),
+    "h2g_debug_assigned_per": ([SZ, ctypes.POINTER(I32)], I32),
+    "h2g_debug_assigned_to_fr_dev": ([VP, SZ, VP, VP, SZ, VP, I32, VP], I32),
+    "h2g_create_proof_assigned": ([U64, U64, VP, VP, ctypes.c_char_p, SZ, ctypes.POINTER(SZ)], I32),
 }
 
 TRANSCRIPTS = {"blake2b": 0, "keccak256": 1}  # Blake2bWrite / Keccak256Write (h2g_pk_set_transcript)
@@ -494,6 +499,49 @@ def batch_invert(a):
     return a
 
 
+def _assigned_args(num, index, den):
+    num = np.ascontiguousarray(num, dtype=np.uint64)
+    idx = np.ascontiguousarray(index, dtype=np.uint64).reshape(-1)
+    dn = np.ascontiguousarray(den, dtype=np.uint64).reshape(-1, 4)
+    assert len(idx) == len(dn), "one denominator per listed cell"
+    return num, idx, dn
+
+
+def assigned_to_fr(num, index, den, out=None):
+    """h2g_assigned_to_fr (batch_invert_assigned, halo2_frontend/src/circuit.rs:363-404): num
+    (ncells, 4) numerators, index the Rational cells' flat indices (strictly increasing), den
+    (len(index), 4) their denominators -> out[index[j]] = num[index[j]] / den[j] (0 for a zero
+    denominator), out = num elsewhere.  out=None: a new array; out=num converts in place."""
+    num, idx, dn = _assigned_args(num, index, den)
+    if out is None:
+        out = np.zeros_like(num)
+    assert out.shape == num.shape
+    check(lib().h2g_assigned_to_fr(p64(num), num.size // 4, p64(idx) if len(idx) else None,
+                                   p64(dn) if len(dn) else None, len(idx), p64(out)))
+    return out
+
+
+def assigned_to_fr_dev(d_num, ncells, d_index, d_den, nden, d_out, stream=None):
+    """h2g_assigned_to_fr_dev: the same on device pointers (16-byte aligned), asynchronous on
+    stream; d_out == d_num converts in place"""
+    check(lib().h2g_assigned_to_fr_dev(VP(d_num), ncells, VP(d_index), VP(d_den), nden, VP(d_out),
+                                       VP(stream) if stream else None))
+
+
+def debug_assigned_per(nden):
+    """h2g_debug_assigned_per: the denominators per thread the size rule takes for nden (host only)"""
+    per = I32(0)
+    check(lib().h2g_debug_assigned_per(nden, ctypes.byref(per)))
+    return per.value
+
+
+def debug_assigned_to_fr_dev(d_num, ncells, d_index, d_den, nden, d_out, per=0, stream=None):
+    """h2g_debug_assigned_to_fr_dev (test seam): assigned_to_fr_dev with `per` denominators per
+    thread (2, 4, 8, 16; 0 = the size rule)"""
+    check(lib().h2g_debug_assigned_to_fr_dev(VP(d_num), ncells, VP(d_index), VP(d_den), nden, VP(d_out), per,
+                                             VP(stream) if stream else None))
+
+
 def u32_exclusive_scan_dev(d_in, d_out, n, stream=None):
     """exclusive prefix sum of n u32 on the device (in place when d_in == d_out)"""
     check(lib().h2g_u32_exclusive_scan_dev(VP(d_in), VP(d_out), n, VP(stream) if stream else None))
@@ -640,6 +688,58 @@ def witness_fill_multi(num_advice, n, fns):
         return single[circuit](ctx, phase, ch_p, adv_p)
 
     cb.num_challenges = 0
+    return cb
+
+
+class AssignedDens(ctypes.Structure):
+    """struct h2g_assigned_dens (include/h2g.h)"""
+    _fields_ = [("index", VP), ("den", VP), ("count", SZ)]
+
+
+# h2g_assigned_source.fill(ctx, circuit, phase, challenges, advice, dens)
+ASSIGNED_FILL = ctypes.CFUNCTYPE(ctypes.c_int, VP, U32, U32, U64P, U64P, ctypes.POINTER(AssignedDens))
+
+
+class AssignedSource(ctypes.Structure):
+    """struct h2g_assigned_source (include/h2g.h)"""
+    _fields_ = [("ctx", VP), ("fill", ASSIGNED_FILL)]
+
+
+def assigned_fill(num_advice, n, fns):
+    """fns[c](phase, challenges) -> ({column: numerators}, index, den) per circuit c as an
+    ASSIGNED_FILL callback: the columns as witness_fill takes them, index the flat cell indices
+    (column * n + row, strictly increasing) of the phase's Rational cells and den their
+    denominators (None or empty: no divisions).  The arrays handed to the prover stay in
+    cb.keep, alive until the caller drops the callback."""
+    import h2g_circuit as hc
+
+    def cb(_ctx, circuit, phase, ch_p, adv_p, dens_p):
+        try:
+            if circuit >= len(fns):
+                return 1
+            nch = cb.num_challenges
+            ch = np.ctypeslib.as_array(ch_p, shape=(max(nch, 1), 4))[:nch] if nch else np.zeros((0, 4), np.uint64)
+            adv = np.ctypeslib.as_array(adv_p, shape=(num_advice, n, 4))
+            cols, index, den = fns[circuit](int(phase), hc.mont_to_ints(ch))
+            for col, vals in cols.items():
+                adv[col, : len(vals)] = vals
+            d = dens_p.contents
+            d.index, d.den, d.count = None, None, 0
+            if index is not None and len(index):
+                idx = np.ascontiguousarray(index, dtype=np.uint64).reshape(-1)
+                dn = np.ascontiguousarray(den, dtype=np.uint64).reshape(-1, 4)
+                if len(idx) != len(dn):
+                    raise ValueError("one denominator per listed cell")
+                cb.keep.append((idx, dn))
+                d.index, d.den, d.count = idx.ctypes.data, dn.ctypes.data, len(idx)
+            return 0
+        except Exception:  # noqa: BLE001 -- reported to the prover as a failed witness
+            import traceback
+            traceback.print_exc()
+            return 1
+
+    cb.num_challenges = 0
+    cb.keep = []
     return cb
 
 
@@ -1020,6 +1120,18 @@ class ProvingKey:
         seed), "native" = the same generator behind the h2g_rng callbacks (h2g_rng_chacha20: the
         caller-RNG path), else an object with fill_bytes(n) (and optionally random_fr()); fills: per-circuit
         fill(phase, challenges) -> {column: values} witness sources."""
+        return self._create_proof_multi(wits, seed, rng, fills, None, vanishing_threads, multiopen, advice_dev_ptrs,
+                                        transcript)
+
+    def create_proof_assigned(self, fills, wits, seed=bytes([7] * 32), rng=None, vanishing_threads=8,
+                              multiopen="shplonk", transcript="blake2b"):
+        """h2g_create_proof_assigned: create_proof_multi with the witness as Assigned cells,
+        evaluated on the device.  fills[c](phase, challenges) -> ({column: numerators}, index,
+        den) (see assigned_fill); wits supply the instance columns.  -> proof bytes"""
+        return self._create_proof_multi(wits, seed, rng, None, fills, vanishing_threads, multiopen, None, transcript)
+
+    def _create_proof_multi(self, wits, seed, rng, fills, assigned, vanishing_threads, multiopen, advice_dev_ptrs,
+                            transcript):
         check(lib().h2g_pk_set_multiopen(self.handle, {"shplonk": 0, "gwc": 1}[multiopen]))
         check(lib().h2g_pk_set_transcript(self.handle, TRANSCRIPTS[transcript]))
         circ = self.circ
@@ -1031,7 +1143,7 @@ class ProvingKey:
         for c, wit in enumerate(wits):
             if advice_dev_ptrs is not None:
                 adv_arr[c] = advice_dev_ptrs[c]
-            elif fills is None:
+            elif fills is None and assigned is None:
                 a = np.ascontiguousarray(wit.advice, dtype=np.uint64)
                 keep.append(a)
                 adv_arr[c] = a.ctypes.data if a.size else None
@@ -1042,7 +1154,8 @@ class ProvingKey:
             lens_arr[c] = lens.ctypes.data
         inp = ProveInputs()
         inp.num_circuits = nc
-        inp.advice = ctypes.cast(adv_arr, ctypes.POINTER(VP))
+        if assigned is None:
+            inp.advice = ctypes.cast(adv_arr, ctypes.POINTER(VP))
         inp.advice_on_device = 1 if advice_dev_ptrs is not None else 0
         inp.instance = ctypes.cast(ins_arr, ctypes.POINTER(VP))
         inp.instance_lens = ctypes.cast(lens_arr, ctypes.POINTER(VP))
@@ -1054,6 +1167,13 @@ class ProvingKey:
             src = WitnessSourceMulti(None, cfn)
             keep += [cb, cfn, src]
             inp.witness = ctypes.pointer(src)
+        asrc = None
+        if assigned is not None:
+            acb = assigned_fill(circ.num_advice, circ.n, assigned)
+            acb.num_challenges = circ.num_challenges
+            acfn = ASSIGNED_FILL(acb)
+            asrc = AssignedSource(None, acfn)
+            keep += [acb, acfn, asrc]  # acb.keep: every (index, den) handed out, until the call returns
         native_rng = None
         if isinstance(rng, str) and rng == "native":  # the library's ChaCha20Rng behind the callbacks
             r = Rng()
@@ -1075,8 +1195,12 @@ class ProvingKey:
         buf = ctypes.create_string_buffer(cap)
         ln = SZ()
         try:
-            check(lib().h2g_create_proof_multi(self.params.handle, self.handle, ctypes.byref(inp), buf, cap,
-                                               ctypes.byref(ln)))
+            if asrc is not None:
+                check(lib().h2g_create_proof_assigned(self.params.handle, self.handle, ctypes.byref(inp),
+                                                      ctypes.byref(asrc), buf, cap, ctypes.byref(ln)))
+            else:
+                check(lib().h2g_create_proof_multi(self.params.handle, self.handle, ctypes.byref(inp), buf, cap,
+                                                   ctypes.byref(ln)))
         finally:
             if native_rng is not None:
                 lib().h2g_rng_free(native_rng.value)
