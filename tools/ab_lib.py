@@ -3,6 +3,9 @@
 copy of e.g. csrc/prover.cpp from an older commit) with the current build's flags and link
 it with the current build's other objects (those of build_lib.sources(), so an object a
 removed source left in build/ is not linked) into lib_ab/libh2g_<tag>.so.
+A revision that spans several sources (or adds or removes one) is not compared this way:
+build the parent commit's whole library from a worktree of it (`git worktree add`, then its
+build_lib.py) and pass that libh2g.so as H2G_LIB (tools/ab_env.py).
 usage: python tools/ab_lib.py TAG SRC_FILE OBJ_TO_REPLACE   (e.g. prev /tmp/prover.cpp prover.cpp)"""
 import os
 import subprocess

@@ -1,6 +1,7 @@
 // prover_state.h -- what the prover's translation units share (internal: included only by
-// params.cpp, commit.cpp, keygen.cpp, spmd.cpp, prover.cpp, pk_serde.cpp, check_witness.cpp,
-// verifier.cpp, g1_fft.hip, and through multiopen.h by multiopen.cpp and kzg.cpp):
+// params.cpp, commit.cpp, keygen.cpp, spmd.cpp, pk_serde.cpp, check_witness.cpp, verifier.cpp,
+// g1_fft.hip, through multiopen.h by multiopen.cpp and kzg.cpp, and through proof_run.h by
+// prover.cpp and prover_lookup.cpp):
 // the params / proving-key / workspace objects, the library's globals and the prototypes of
 // the functions that cross files.  Each global is defined in the file that owns it.
 #pragma once
@@ -152,6 +153,7 @@ struct CircuitWs {
   };
   std::vector<SubTables> sub;
   int64_t sub_key = -1;
+  SubTables whole() const { return SubTables{d_load_col, d_z, d_perm_v, d_lookups, d_shuffles}; }  // the d_* tables
   ~CircuitWs() {
     if (!wit_pin) return;
     if (wit_pin_pinned) (void)hipHostFree(wit_pin);
