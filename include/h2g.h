@@ -177,6 +177,37 @@ typedef struct h2g_ntt_plan {
 } h2g_ntt_plan;
 int h2g_debug_ntt_plan(uint32_t log_n, uint64_t n_in, uint64_t out_len, int count, int in_twist, int cus,
                        int epilogue_one, h2g_ntt_plan* plan);
+/* test seam: what an MSM of n points decides before it allocates or launches -- the plan
+ * every MSM pipeline runs from, as a function of the call's shape alone.  c: window bits, 0 =
+ * the library's choice for n (variable- or fixed-base); fixed: fixed-base tables (ceil(255 / c)
+ * windows of balanced widths sharing one bucket set per MSM) with nbatch MSMs in one pipeline
+ * (1..64; variable-base: 1); item_len: entries per accumulation chunk, 0 = the adaptive rule.
+ * H2G_ERR_ARG (plan untouched) for a shape the pipeline refuses: the batch range, n W nbatch
+ * >= 2^31 entries, more than 2048 coarse bins (sets x 2^(c-1) > 2^22 buckets), more than 256
+ * bucket sets.  Host only: needs no h2g_init. */
+typedef struct h2g_msm_plan {
+  uint64_t total;      /* entry bound n W nbatch */
+  uint64_t nb_eff;     /* buckets most windows can reach (chunk rule) */
+  uint64_t nchunks;    /* the most accumulation chunks: grids and boundary slots are sized for it */
+  uint64_t bytes[10];  /* workspace buffers: entries / whole buckets, values, big-bucket items, boundary
+                          slots, buckets, reduction levels, window sums, counters, multi-item buckets,
+                          items' partial sums */
+  uint64_t scratch_words; /* 32-bit words of the partition's count / offset scratch */
+  uint32_t c, W;          /* window bits, windows */
+  uint32_t fixed, nbatch;
+  uint32_t WB, NB, nbt;   /* bucket sets, buckets per set 2^(c-1), their product */
+  uint32_t chunk_len;     /* the host's entries per chunk */
+  uint32_t chunk_adapt;   /* 1: the device shortens it when few entries exist */
+  uint32_t fb, ncoarse, kblocks; /* partition: fine bits, coarse bins, 1024-key scan blocks */
+  uint32_t staged;        /* the partition's second round in its LDS-staged form */
+  uint32_t fixup_q;       /* lanes per bucket of the fixup: 4 or 1 */
+  uint32_t red_plane;     /* reduction: 1 bit planes, 0 per-group scalar multiplications (rscale) */
+  uint32_t plane_q, plane_lb, rgp, e0, m1p, nblk_p; /* planes: lanes per group (4, 1), log2 groups per
+                             block, buckets per group and its log2, groups and blocks per set; 0 under rscale */
+  uint32_t m1, nblk;      /* rscale: groups of 8 buckets and blocks of 256 groups per set; 0 under planes */
+  uint32_t reserved;
+} h2g_msm_plan;
+int h2g_debug_msm_plan(uint64_t n, int c, int fixed, int nbatch, uint32_t item_len, h2g_msm_plan* plan);
 
 /* ---- Polynomial<F, B> arithmetic (halo2_backend/src/poly.rs:200-276) ---------
  * op: 0 add a+b, 1 sub a-b, 2 mul a*b, 3 scale a*c, 4 sub_const a-c, 5 add_const a+c,

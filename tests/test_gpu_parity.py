@@ -134,6 +134,71 @@ def test_msm_window_sizes(window_bits):
     assert np.array_equal(h2g.msm_dev_host(dsc.ptr, dbs.ptr, n, window_bits), want)  # host-side combine
 
 
+# (what the shape must select in h2g.debug_msm_plan, the shape): every reduction and fixup
+# variant msm_plan can choose, at 3000 points
+MSM_VARIANTS = {
+    "plane_q4_rgp1": (dict(red="plane", plane_q=4, plane_lb=6, rgp=1), dict(c=9)),
+    "plane_q4_rgp2": (dict(red="plane", plane_q=4, plane_lb=6, rgp=2), dict(c=13)),
+    "plane_q4_rgp4": (dict(red="plane", plane_q=4, plane_lb=6, rgp=4), dict(c=14)),
+    "plane_q4_rgp8": (dict(red="plane", plane_q=4, plane_lb=6, rgp=8), dict(c=19, fixed=True)),
+    "plane_q1": (dict(red="plane", plane_q=1, plane_lb=8, rgp=8), dict(c=17)),
+    "rscale": (dict(red="rscale", m1=1 << 18, nblk=1024), dict(c=22, fixed=True)),
+    "fixup_quad": (dict(fixup_q=4), dict(c=9)),
+    "fixup_lane": (dict(fixup_q=1), dict(c=13)),
+}
+MSM_VARIANT_N = 3000
+
+
+@pytest.fixture(scope="module")
+def variant_inputs(engine):
+    """bases, and (scalars, oracle result) for random scalars and for ones (every digit in one
+    bucket): computed once for all the cases"""
+    r = rng(99)
+    n = MSM_VARIANT_N
+    d_bases = _srs(n, O.random_fr(r, 1)[0])
+    bases = d_bases.download((n, 8))
+    runs = []
+    for sc in (O.random_fr(r, n), _skewed("ones", r, n)):
+        runs.append((h2g.DevBuf.from_array(sc), O.msm_best(sc, bases, 8)))
+    yield d_bases, runs
+    for d_sc, _ in runs:
+        d_sc.close()
+    d_bases.close()
+
+
+@pytest.mark.parametrize("name", sorted(MSM_VARIANTS))
+def test_msm_every_reachable_variant(name, variant_inputs):
+    """Each kernel variant the MSM's plan can select, at the smallest shape that selects it:
+    first that the shape still selects it (a moved threshold fails here instead of silently
+    losing the coverage; tests/test_msm_plan_cpu.py pins the rule itself), then one MSM of
+    random scalars and one of ones against the oracle.  Variable-base shapes run with the
+    device's and with the host's final combine (msm_dev, msm_dev_host); fixed-base shapes run
+    against a table (msm_with_cached_base_dev), the one entry fixed-base MSMs have -- its
+    final combine is the host's.  The rscale scheme exists only there: msm_dev refuses c >= 20
+    (13 x 2^19 buckets; test_msm_plan_cpu.py::test_first_refused_partition).
+    The batched fixed-base pipeline (more than one bucket set against a table) has no public
+    entry of its own and stays covered by the prover tests, whose commitments run through it."""
+    want_plan, shape = MSM_VARIANTS[name]
+    n = MSM_VARIANT_N
+    pl = h2g.debug_msm_plan(n, **shape)
+    assert {k: pl[k] for k in want_plan} == want_plan, name
+    d_bases, runs = variant_inputs
+    if shape.get("fixed"):
+        h = h2g.base_descriptor_dev(d_bases.ptr, n, shape["c"])
+        try:
+            for d_sc, want in runs:
+                assert np.array_equal(h2g.msm_with_cached_base_dev(d_sc.ptr, n, h, 0), want), name
+        finally:
+            h2g.descriptor_free(h)
+        return
+    dout = h2g.DevBuf(64)
+    for d_sc, want in runs:
+        h2g.msm_dev(d_sc.ptr, d_bases.ptr, n, dout.ptr, window_bits=shape["c"])
+        assert np.array_equal(dout.download(8), want), name
+        assert np.array_equal(h2g.msm_dev_host(d_sc.ptr, d_bases.ptr, n, shape["c"]), want), name
+    dout.close()
+
+
 @pytest.mark.parametrize("k", [20, 22])
 def test_msm_full_size_srs_identity(k):
     """sum_i c_i [s^i] G == [c(s)] G at BASELINE sizes (no O(n) CPU MSM needed)."""

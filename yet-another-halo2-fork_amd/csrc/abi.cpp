@@ -140,7 +140,7 @@ int msm_dev_impl(Device* d, const void* sc, const void* bs, size_t n, int c, voi
 // (msm_windows_host_finish): the affine result, and whether it is the identity
 static int msm_windows_to_host(Device* d, int W, uint64_t* out, int* is_id, hipStream_t st) {
   if (!d->h_windows) HIPCHK(hipHostMalloc(&d->h_windows, 256 * sizeof(G1xyzz), hipHostMallocDefault));
-  HIPCHK(hipMemcpyAsync(d->h_windows, d->msm.windows, (size_t)W * sizeof(G1xyzz), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(d->h_windows, d->msm.windows.p, (size_t)W * sizeof(G1xyzz), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   const G1Affine r = msm_windows_host_finish(reinterpret_cast<const G1xyzz*>(d->h_windows), W, d->msm.last_c);
   std::memcpy(out, &r, 64);
@@ -220,7 +220,7 @@ int msm_fixed_launch_batch(Device* d, const void* const* sc, int nb, const MsmFi
     for (int b = 0; b < nb; b++) list.p[b] = reinterpret_cast<const Fr*>(sc[b]);
     if (nb == 1) HIPCHK(msm_run_fixed(list.p[0], fb, off, n, &d->mws[slot], nullptr, ms, pe));
     else HIPCHK(msm_run_fixed_batch(list, nb, fb, off, n, &d->mws[slot], ms, pe));
-    const G1xyzz* win = reinterpret_cast<const G1xyzz*>(d->mws[slot].windows);
+    const G1xyzz* win = reinterpret_cast<const G1xyzz*>(d->mws[slot].windows.p);
     for (int b = 0; b < nb; b++)
       HIPCHK(hipMemcpyAsync(host + rings[b], win + b, sizeof(G1xyzz), hipMemcpyDeviceToHost, ms));
   }
@@ -881,6 +881,28 @@ int h2g_debug_ntt_plan(uint32_t log_n, uint64_t n_in, uint64_t out_len, int coun
   o.first_grid = pl.first_grid;
   for (int p = 0; p < 6; p++) o.pgrid[p] = pl.pgrid[p];
   *plan = o;
+  return H2G_OK;
+}
+
+// test seam: msm_plan, the function every MSM pipeline runs from (host only, no device state)
+int h2g_debug_msm_plan(uint64_t n, int c, int fixed, int nbatch, uint32_t item_len, h2g_msm_plan* plan) {
+  static_assert(sizeof(h2g_msm_plan) == sizeof(MsmPlan) && sizeof(MsmPlan) == 14 * 8 + 24 * 4 &&
+                    sizeof(MsmBytes) == sizeof(h2g_msm_plan::bytes) &&
+                    offsetof(h2g_msm_plan, bytes) == offsetof(MsmPlan, bytes) &&
+                    offsetof(h2g_msm_plan, scratch_words) == offsetof(MsmPlan, scratch_words) &&
+                    offsetof(h2g_msm_plan, c) == offsetof(MsmPlan, c) &&
+                    offsetof(h2g_msm_plan, chunk_len) == offsetof(MsmPlan, L) &&
+                    offsetof(h2g_msm_plan, fixup_q) == offsetof(MsmPlan, fixup_q) &&
+                    offsetof(h2g_msm_plan, nblk_p) == offsetof(MsmPlan, nblk_p) &&
+                    offsetof(h2g_msm_plan, reserved) == offsetof(MsmPlan, reserved),
+                "h2g_msm_plan mirrors MsmPlan");
+  if (!plan) return fail(H2G_ERR_ARG, "debug_msm_plan: null argument");
+  if (c < 0) return fail(H2G_ERR_ARG, "debug_msm_plan: negative c");
+  if (c == 0) c = fixed ? msm_choose_c_fixed(n) : msm_choose_c(n);
+  MsmPlan pl;
+  if (!msm_plan(n, c, msm_windows_for(c), fixed, nbatch, item_len, &pl))
+    return fail(H2G_ERR_ARG, "debug_msm_plan: a shape the MSM refuses");
+  std::memcpy(plan, &pl, sizeof(pl));
   return H2G_OK;
 }
 

@@ -23,10 +23,12 @@
 //   4. fixup      : buckets spanning chunks sum their boundary slots (one thread,
 //                   or items of 64 pieces for buckets spanning more chunks)
 //   5. reduction  : sum_j (j+1) B_j per bucket set: group running sums, then bit planes
-//                   (or per-group scalar multiplications for c = 22 sets) and trees
+//                   (or per-group scalar multiplications for c >= 22 sets) and trees
 //   6. final      : Horner over windows (c doublings each), to affine -- on the
 //                   host for host-returning entry points (a single-lane chain of
 //                   ~250 doublings is latency-bound on the GPU), else one device lane.
+// msm_plan (a pure host function) decides every size, grid and kernel variant from the
+// MSM's shape; msm_pipeline allocates and launches from that plan alone.
 // The result is the unique affine point, so it is bit-identical to any other
 // correct MSM (e.g. the CPU restatement in oracle/) regardless of summation order.
 #include <algorithm>
@@ -69,17 +71,6 @@ int msm_choose_c(size_t n) {
     }
   }
   return best_c;
-}
-
-__device__ __forceinline__ G1Affine ld_aff(const G1Affine* p) {
-  const uint4* q = reinterpret_cast<const uint4*>(p);
-  uint4 a = q[0], b = q[1], c = q[2], d = q[3];
-  G1Affine r;
-  r.x.l[0] = a.x; r.x.l[1] = a.y; r.x.l[2] = a.z; r.x.l[3] = a.w;
-  r.x.l[4] = b.x; r.x.l[5] = b.y; r.x.l[6] = b.z; r.x.l[7] = b.w;
-  r.y.l[0] = c.x; r.y.l[1] = c.y; r.y.l[2] = c.z; r.y.l[3] = c.w;
-  r.y.l[4] = d.x; r.y.l[5] = d.y; r.y.l[6] = d.z; r.y.l[7] = d.w;
-  return r;
 }
 
 // Quad-cooperative XYZZ arithmetic for the latency-bound reduction kernels ----------
@@ -167,34 +158,11 @@ __device__ __forceinline__ G1xyzz29 xyzz29_add_q4(const G1xyzz29& p, const G1xyz
   r.ZZZ = quad_bcast29<1>(m);
   return r;
 }
-__device__ G1xyzz29 xyzz29_mul_u32_q4(const G1xyzz29& p, uint32_t k) {
-  if (k == 0) return xyzz29_identity();
-  int top = 31;
-  while (!((k >> top) & 1)) top--;
-  G1xyzz29 acc = p;
-  for (int b = top - 1; b >= 0; b--) {
-    acc = xyzz29_dbl_q4(acc);
-    if ((k >> b) & 1) acc = xyzz29_add_q4(acc, p);
-  }
-  return acc;
-}
 
-// The back-end's point type (msm_part.h RedPoint) and its operations: F29 accumulators in
-// the back-end class
-__device__ __forceinline__ RedPoint rp_identity() { return xyzz29_identity(); }
-__device__ __forceinline__ RedPoint rp_add(const RedPoint& a, const RedPoint& b) { return xyzz29_add(a, b); }
-__device__ __forceinline__ RedPoint rp_dbl(const RedPoint& a) { return xyzz29_dbl(a); }
-__device__ __forceinline__ RedPoint rp_add_q4(const RedPoint& a, const RedPoint& b) { return xyzz29_add_q4(a, b); }
-__device__ __forceinline__ RedPoint rp_dbl_q4(const RedPoint& a) { return xyzz29_dbl_q4(a); }
-__device__ __forceinline__ RedPoint rp_mul_u32(const RedPoint& a, uint32_t k) { return xyzz29_mul_u32(a, k); }
-__device__ __forceinline__ RedPoint rp_mul_u32_q4(const RedPoint& a, uint32_t k) { return xyzz29_mul_u32_q4(a, k); }
-__device__ __forceinline__ G1xyzz rp_to_xyzz(const RedPoint& a) { return xyzz_from29(a); }
-// an accumulation output (bucket or boundary slot) into the back-end class
-__device__ __forceinline__ RedPoint rp_from_acc(const AccPoint& a) { return xyzz29_reduce(a); }
-// 16-B moves of back-end points in global memory
-__device__ __forceinline__ RedPoint ld_rp(const RedPoint* p) { return ld_acc(p); }
-__device__ __forceinline__ void st_rp(RedPoint* p, const RedPoint& v) { st_acc(p, v); }
-
+// AccPoint / RedPoint (msm_part.h) are both G1xyzz29: the accumulation's raw F29 accumulators,
+// and the same coordinates reduced into f29.h's back-end class (xyzz29_reduce), which the
+// fixup's and the reduction's additions take.
+//
 // Buckets spanning chunks, one thread per bucket: the piece in its first chunk t0 is
 // that chunk's last run (slot 1) unless the bucket starts the chunk (slot 0); every
 // later chunk holds it as its first run (slot 0).  Buckets over more than MSM_SMALL
@@ -204,7 +172,7 @@ __device__ __forceinline__ void st_rp(RedPoint* p, const RedPoint& v) { st_acc(p
 // entries per bucket at c = 22; a column of equal values: n entries per bucket).
 // (the slots hold raw F29 accumulators, brought into the back-end class here)
 __device__ __forceinline__ RedPoint msm_piece(const AccPoint* bnd, uint32_t t, uint32_t t0, uint32_t bs, uint32_t L) {
-  return rp_from_acc(ld_acc(bnd + 2 * (size_t)t + ((t == t0 && bs != t0 * L) ? 1 : 0)));
+  return xyzz29_reduce(ld_acc(bnd + 2 * (size_t)t + ((t == t0 && bs != t0 * L) ? 1 : 0)));
 }
 
 static constexpr uint32_t MSM_GROUP = 16;            // lanes per item
@@ -268,9 +236,9 @@ msm_fixup_kernel(const AccPoint* __restrict__ bnd, const uint32_t* __restrict__ 
   }
   ibase = __shfl(ibase, 0, 64);
   mbase = __shfl(mbase, 0, 64);
-  if (b < nbt && be <= bs && lead) st_rp(buckets + b, rp_identity());  // empty (no fill of buckets[])
+  if (b < nbt && be <= bs && lead) st_acc(buckets + b, xyzz29_identity());  // empty (no fill of buckets[])
   // a bucket the accumulation wrote whole: its raw accumulator, into the back-end class
-  if (b < nbt && be > bs && np == 0 && lead) st_rp(buckets + b, rp_from_acc(ld_acc(whole + b)));
+  if (b < nbt && be > bs && np == 0 && lead) st_acc(buckets + b, xyzz29_reduce(ld_acc(whole + b)));
   if (np == 0) return;
   if (np > small) {
     if (!cnt) return;  // the quad's other lanes
@@ -288,10 +256,10 @@ msm_fixup_kernel(const AccPoint* __restrict__ bnd, const uint32_t* __restrict__ 
   }
   RedPoint acc = msm_piece(bnd, t0, t0, bs, L);
   for (uint32_t t = t0 + 1; t <= t1; t++) {
-    if constexpr (Q == 4) acc = rp_add_q4(acc, msm_piece(bnd, t, t0, bs, L));
-    else acc = rp_add(acc, msm_piece(bnd, t, t0, bs, L));
+    if constexpr (Q == 4) acc = xyzz29_add_q4(acc, msm_piece(bnd, t, t0, bs, L));
+    else acc = xyzz29_add(acc, msm_piece(bnd, t, t0, bs, L));
   }
-  if (lead) st_rp(buckets + b, acc);
+  if (lead) st_acc(buckets + b, acc);
 }
 
 // MSM_GROUP lanes per item (4 items per wave, persistent grid): each lane sums up to
@@ -313,12 +281,12 @@ msm_big_item_kernel(const AccPoint* __restrict__ bnd, const uint32_t* __restrict
   for (uint32_t q0 = (blockIdx.x * (MSM_THREADS / 64) + (threadIdx.x >> 6)) * per_wave; q0 < nitems;
        q0 += stride) {
     const uint32_t q = q0 + lane / MSM_GROUP;
-    RedPoint acc = rp_identity();
+    RedPoint acc = xyzz29_identity();
     MsmBigItem it = {0, 0, 0, 0};
     if (q < nitems) {
       it = items[q];
       const uint32_t bs = koff[it.b], t0 = bs / L;
-      for (uint32_t t = it.tb + g; t < it.te; t += MSM_GROUP) acc = rp_add(acc, msm_piece(bnd, t, t0, bs, L));
+      for (uint32_t t = it.tb + g; t < it.te; t += MSM_GROUP) acc = xyzz29_add(acc, msm_piece(bnd, t, t0, bs, L));
     }
     w[g] = acc;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -326,7 +294,7 @@ msm_big_item_kernel(const AccPoint* __restrict__ bnd, const uint32_t* __restrict
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll 1
     for (uint32_t h = MSM_GROUP / 2; h > 0; h >>= 1) {
-      if (g < h) w[g] = rp_add(w[g], w[g + h]);
+      if (g < h) w[g] = xyzz29_add(w[g], w[g + h]);
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -356,7 +324,7 @@ msm_big_combine_kernel(const uint4* __restrict__ multi, const uint32_t* __restri
     const uint4 m = multi[q];  // (bucket, first item, items)
     if (m.z > COMBINE_LANE) continue;
     RedPoint acc = partial[m.y];
-    for (uint32_t i = 1; i < m.z; i++) acc = rp_add(acc, partial[m.y + i]);
+    for (uint32_t i = 1; i < m.z; i++) acc = xyzz29_add(acc, partial[m.y + i]);
     buckets[m.x] = acc;
   }
   RedPoint* w = sh + (threadIdx.x & ~63u);
@@ -364,15 +332,15 @@ msm_big_combine_kernel(const uint4* __restrict__ multi, const uint32_t* __restri
   for (uint32_t q = blockIdx.x * (MSM_THREADS / 64) + (threadIdx.x >> 6); q < nm; q += nwaves) {
     const uint4 m = multi[q];  // (bucket, first item, items)
     if (m.z <= COMBINE_LANE) continue;  // uniform across the wave
-    RedPoint acc = rp_identity();
-    for (uint32_t i = lane; i < m.z; i += 64) acc = rp_add(acc, partial[m.y + i]);
+    RedPoint acc = xyzz29_identity();
+    for (uint32_t i = lane; i < m.z; i += 64) acc = xyzz29_add(acc, partial[m.y + i]);
     w[lane] = acc;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll 1
     for (uint32_t h = 32; h > 0; h >>= 1) {
-      if (lane < h) w[lane] = rp_add(w[lane], w[lane + h]);
+      if (lane < h) w[lane] = xyzz29_add(w[lane], w[lane + h]);
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -403,11 +371,11 @@ msm_rgroup_kernel(const RedPoint* __restrict__ B, uint32_t NB, uint32_t m1, RedP
   const uint32_t g = blockIdx.x * MSM_THREADS + threadIdx.x;
   if (g >= m1) return;
   const RedPoint* b = B + (size_t)w * NB;
-  RedPoint racc = rp_identity(), sacc = rp_identity();
+  RedPoint racc = xyzz29_identity(), sacc = xyzz29_identity();
   for (int t = RG - 1; t >= 0; t--) {
     const uint32_t j = g * RG + t;
-    if (j < NB) racc = rp_add(racc, b[j]);
-    sacc = rp_add(sacc, racc);
+    if (j < NB) racc = xyzz29_add(racc, b[j]);
+    sacc = xyzz29_add(sacc, racc);
   }
   S[(size_t)w * m1 + g] = sacc;
   R[(size_t)w * m1 + g] = racc;
@@ -420,86 +388,40 @@ msm_rscale_kernel(const RedPoint* __restrict__ S, const RedPoint* __restrict__ R
   __shared__ RedPoint sh[MSM_THREADS];
   const uint32_t w = blockIdx.y;
   const uint32_t g = blockIdx.x * MSM_THREADS + threadIdx.x;
-  RedPoint v = rp_identity();
+  RedPoint v = xyzz29_identity();
   if (g < m1) {
     v = S[(size_t)w * m1 + g];
-    if (g) v = rp_add(v, rp_mul_u32(R[(size_t)w * m1 + g], g * RG));
+    if (g) v = xyzz29_add(v, xyzz29_mul_u32(R[(size_t)w * m1 + g], g * RG));
   }
   sh[threadIdx.x] = v;
   __syncthreads();
   for (int h = MSM_THREADS / 2; h > 0; h >>= 1) {
-    if ((int)threadIdx.x < h) sh[threadIdx.x] = rp_add(sh[threadIdx.x], sh[threadIdx.x + h]);
+    if ((int)threadIdx.x < h) sh[threadIdx.x] = xyzz29_add(sh[threadIdx.x], sh[threadIdx.x + h]);
     __syncthreads();
   }
   if (threadIdx.x == 0) part[(size_t)w * nblk + blockIdx.x] = sh[0];
 }
 
-// the same three kernels with one quad per thread above (xyzz29_*_q4): a quad per group,
-// 64 groups per block; taken when the groups cannot fill the SIMDs (small MSMs, e.g. the
-// 2^19-2^20-point slabs of a sharded proof), and always for the final tree
-__global__ void __launch_bounds__(MSM_THREADS)
-msm_rgroup_q4_kernel(const RedPoint* __restrict__ B, uint32_t NB, uint32_t m1, RedPoint* __restrict__ S,
-                     RedPoint* __restrict__ R) {
-  H2G_SETPRIO(H2G_PRIO_RED);
-  const uint32_t w = blockIdx.y;
-  const uint32_t g = (blockIdx.x * MSM_THREADS + threadIdx.x) >> 2;
-  if (g >= m1) return;  // the whole quad
-  const RedPoint* b = B + (size_t)w * NB;
-  RedPoint racc = rp_identity(), sacc = rp_identity();
-  for (int t = RG - 1; t >= 0; t--) {
-    const uint32_t j = g * RG + t;
-    if (j < NB) racc = rp_add_q4(racc, b[j]);
-    sacc = rp_add_q4(sacc, racc);
-  }
-  if ((threadIdx.x & 3) == 0) {
-    S[(size_t)w * m1 + g] = sacc;
-    R[(size_t)w * m1 + g] = racc;
-  }
-}
-
-static constexpr uint32_t Q4_GROUPS = MSM_THREADS / 4;  // quads per block
-
-__global__ void __launch_bounds__(MSM_THREADS)
-msm_rscale_q4_kernel(const RedPoint* __restrict__ S, const RedPoint* __restrict__ R, uint32_t m1,
-                     RedPoint* __restrict__ part, uint32_t nblk) {
-  H2G_SETPRIO(H2G_PRIO_RED);
-  __shared__ RedPoint sh[Q4_GROUPS];
-  const uint32_t w = blockIdx.y, qi = threadIdx.x >> 2;
-  const uint32_t g = blockIdx.x * Q4_GROUPS + qi;
-  RedPoint v = rp_identity();
-  if (g < m1) {
-    v = S[(size_t)w * m1 + g];
-    if (g) v = rp_add_q4(v, rp_mul_u32_q4(R[(size_t)w * m1 + g], g * RG));
-  }
-  if ((threadIdx.x & 3) == 0) sh[qi] = v;
-  __syncthreads();
-  for (uint32_t h = Q4_GROUPS / 2; h > 0; h >>= 1) {
-    if (qi < h) {  // sh[qi + h] is not written at this level
-      const RedPoint t = rp_add_q4(sh[qi], sh[qi + h]);
-      if ((threadIdx.x & 3) == 0) sh[qi] = t;
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) part[(size_t)w * nblk + blockIdx.x] = sh[0];
-}
+// the sum of a set's block sums, one quad per term (xyzz29_*_q4): 64 quads per block
+static constexpr uint32_t Q4_GROUPS = MSM_THREADS / 4;
 
 __global__ void __launch_bounds__(MSM_THREADS)
 msm_rfinal_q4_kernel(const RedPoint* __restrict__ part, uint32_t nblk, G1xyzz* __restrict__ windows) {
   H2G_SETPRIO(H2G_PRIO_RED);
   __shared__ RedPoint sh[Q4_GROUPS];
   const uint32_t w = blockIdx.x, qi = threadIdx.x >> 2;
-  RedPoint acc = rp_identity();
-  for (uint32_t i = qi; i < nblk; i += Q4_GROUPS) acc = rp_add_q4(acc, part[(size_t)w * nblk + i]);
+  RedPoint acc = xyzz29_identity();
+  for (uint32_t i = qi; i < nblk; i += Q4_GROUPS) acc = xyzz29_add_q4(acc, part[(size_t)w * nblk + i]);
   if ((threadIdx.x & 3) == 0) sh[qi] = acc;
   __syncthreads();
   for (uint32_t h = Q4_GROUPS / 2; h > 0; h >>= 1) {
     if (qi < h) {
-      const RedPoint t = rp_add_q4(sh[qi], sh[qi + h]);
+      const RedPoint t = xyzz29_add_q4(sh[qi], sh[qi + h]);
       if ((threadIdx.x & 3) == 0) sh[qi] = t;
     }
     __syncthreads();
   }
-  if (threadIdx.x == 0) windows[w] = rp_to_xyzz(sh[0]);  // the host finish reads G1xyzz
+  if (threadIdx.x == 0) windows[w] = xyzz_from29(sh[0]);  // the host finish reads G1xyzz
 }
 
 // 6a'. group weights by bit planes (default when the groups fit 2^16) ----------------------
@@ -512,24 +434,35 @@ msm_rfinal_q4_kernel(const RedPoint* __restrict__ part, uint32_t nblk, G1xyzz* _
 // plain-summed across blocks (plane b < 8) and their totals folded once more by block
 // index (planes 8..15); the last block to finish scales the 16 planes and adds them to
 // sum S.  Two launches (rgroup fused into the first), lane-per-group (Q = 1, 256-group
-// blocks) or quad-cooperative (Q = 4, 64-group blocks) like the group kernels above.
+// blocks) or quad-cooperative (Q = 4, 64-group blocks).
 
 // The plane kernels' additions skip, wave-uniformly, when every lane adds the identity:
 // sets of small or sparse scalars (a batch of 4-bit witness columns fills 15 buckets of
 // 2^16 per set) are mostly empty groups, whose additions the identity test alone, taken
 // per lane inside the formula, does not skip for the wave.
-__device__ __forceinline__ bool rp_is_identity(const RedPoint& a) { return xyzz29_is_identity(a); }
+// a point operation by one lane (Q = 1) or by the four lanes of a quad (Q = 4); apart from
+// padd / pdbl, so that the plane kernels compile to what they always were: with the four calls
+// written inside the skip tests the compiler moved a few of their scalar instructions
+// (profiles/msm_plan/notes.txt)
+template <int Q>
+__device__ __forceinline__ RedPoint qadd(const RedPoint& a, const RedPoint& b) {
+  if constexpr (Q == 4) return xyzz29_add_q4(a, b);
+  else return xyzz29_add(a, b);
+}
+template <int Q>
+__device__ __forceinline__ RedPoint qdbl(const RedPoint& a) {
+  if constexpr (Q == 4) return xyzz29_dbl_q4(a);
+  else return xyzz29_dbl(a);
+}
 template <int Q>
 __device__ __forceinline__ RedPoint padd(const RedPoint& a, const RedPoint& b) {
-  if (!__any(!rp_is_identity(b))) return a;
-  if constexpr (Q == 4) return rp_add_q4(a, b);
-  else return rp_add(a, b);
+  if (!__any(!xyzz29_is_identity(b))) return a;
+  return qadd<Q>(a, b);
 }
 template <int Q>
 __device__ __forceinline__ RedPoint pdbl(const RedPoint& a) {
-  if (!__any(!rp_is_identity(a))) return a;
-  if constexpr (Q == 4) return rp_dbl_q4(a);
-  else return rp_dbl(a);
+  if (!__any(!xyzz29_is_identity(a))) return a;
+  return qdbl<Q>(a);
 }
 
 // in LDS: T[0..len) holds one value per element, len = 2^K <= 512.  Afterwards T[0] is the
@@ -571,7 +504,7 @@ msm_rgroup_plane_kernel(const RedPoint* __restrict__ B, uint32_t NB, uint32_t m1
   const bool b0 = blockIdx.x == 0 && blockIdx.y == 0, bl = blockIdx.x == gridDim.x - 1 && blockIdx.y == 0;
   RED_TS(b0, 0);
   RED_TS(bl, 4);
-  RedPoint racc = rp_identity(), sacc = rp_identity();
+  RedPoint racc = xyzz29_identity(), sacc = xyzz29_identity();
   if (g < m1) {
 #pragma unroll
     for (int t = RGP - 1; t >= 0; t--) {
@@ -638,7 +571,7 @@ msm_rplane_mid_kernel(const RedPoint* __restrict__ planes, uint32_t nblk, int LB
   RED_TS(q == 0 && w == 0, 8);
   RED_TS(q == (uint32_t)LB + 1 && w == 0, 11);
   if (q <= (uint32_t)LB) {
-    RedPoint acc = rp_identity();
+    RedPoint acc = xyzz29_identity();
     for (uint32_t i = e; i < nblk; i += RPM_QUADS) acc = padd<4>(acc, in[i]);
     if (lead) sh[e] = acc;
     __syncthreads();
@@ -658,8 +591,8 @@ msm_rplane_mid_kernel(const RedPoint* __restrict__ planes, uint32_t nblk, int LB
   } else {
     for (uint32_t i = e; i < (1u << K); i += RPM_QUADS)
       if (lead) {
-        if (i < nblk) sh[i] = ld_rp(in + i);
-        else sh[i] = rp_identity();
+        if (i < nblk) sh[i] = ld_acc(in + i);
+        else sh[i] = xyzz29_identity();
       }
     __syncthreads();
     RED_TS(w == 0, 12);
@@ -678,7 +611,7 @@ msm_rplane_mid_kernel(const RedPoint* __restrict__ planes, uint32_t nblk, int LB
   __threadfence();
   RED_TS(w == 0, 14);
   const uint32_t np = (uint32_t)(LB + K);  // planes (<= 18)
-  RedPoint x = rp_identity();
+  RedPoint x = xyzz29_identity();
   if (e < np) {
     x = mid[(size_t)(1 + e) * WB + w];
     for (int i = 0; i < (int)e + e0; i++) x = pdbl<4>(x);
@@ -698,7 +631,7 @@ msm_rplane_mid_kernel(const RedPoint* __restrict__ planes, uint32_t nblk, int LB
     __syncthreads();
   }
   RED_TS(w == 0, 16);
-  if (threadIdx.x == 0) windows[w] = rp_to_xyzz(sh[0]);  // the host finish reads G1xyzz
+  if (threadIdx.x == 0) windows[w] = xyzz_from29(sh[0]);  // the host finish reads G1xyzz
 }
 
 // fixed-base tables: table[w * stride + i] = [2^(offset of window w)] bases[i] -------
@@ -737,24 +670,6 @@ G1Affine msm_windows_host_finish(const G1xyzz* h_windows, int W, int c) {
 }
 
 // ------------------------------------------------------------------------------------
-static hipError_t grow(void** p, size_t bytes) {
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  return hipMalloc(p, bytes > 0 ? bytes : 16);
-}
-
-void msm_free(MsmWorkspace* ws) {
-  void** ptrs[] = {&ws->ent, &ws->vals_out, &ws->item_off, &ws->item_bucket, &ws->partials,
-                   &ws->buckets, &ws->segs, &ws->windows, &ws->result, &ws->total_items, &ws->sort_tmp};
-  for (void** p : ptrs) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-  }
-  for (auto& c : ws->cap) c = 0;
-  ws->sort_tmp_bytes = 0;
-  ws->sort_kcap = 0;
-}
-
 #define H2G_TRY(x)                      \
   do {                                  \
     hipError_t _e = (x);                \
@@ -776,12 +691,6 @@ uint32_t msm_chunk_len(size_t total, size_t nbt) {
   return (uint32_t)L;
 }
 
-// quad-cooperative group kernels (rscale scheme) when the groups leave SIMDs idle: up to
-// 32768 groups over all sets (MSMs up to 2^21 points).  At 65536 groups (2^22) the quad
-// kernels lose even for a lone MSM: reduction 1.07 vs 0.72 ms, C3 k = 22 proof 94.1-94.3
-// vs 90.2-90.3 ms (profiles/r02/ab_q4/).  Quad fixup up to 2^15 buckets (2^16, the
-// 2^19-point slabs: the lane form is faster).
-static constexpr size_t RED_Q4_MAX = 32768;
 #ifndef H2G_PLANE_LB_SMALL  // A/B builds (tools/build_variant.py -DH2G_PLANE_LB_SMALL=8)
 #define H2G_PLANE_LB_SMALL 6
 #endif
@@ -790,29 +699,46 @@ static constexpr int kSmallLB = H2G_PLANE_LB_SMALL;
 #define H2G_PLANE_RGP_LARGE 8
 #endif
 static constexpr int kLargeRGP = H2G_PLANE_RGP_LARGE;
+// Quad fixup up to 2^15 buckets (2^16, the 2^19-point slabs: the lane form is faster).
 static constexpr uint32_t FIXUP_Q4_MAX = 32768;
 
-static hipError_t msm_pipeline(const MsmScalarList& list, int nbatch, const G1Affine* d_bases, size_t n, int c,
-                               int W, int fixed, size_t stride, MsmWorkspace* ws, uint32_t item_len, G1Affine* d_out,
-                               hipStream_t st, MsmPhaseEvents* prof) {
-#define H2G_PHASE(i) \
-  if (prof) H2G_TRY(hipEventRecord(prof->ev[i], st))
-  const uint32_t NB = 1u << (c - 1);
-  if (nbatch < 1 || nbatch > MSM_MAX_BATCH || (!fixed && nbatch != 1)) return hipErrorInvalidValue;
-  const int WB = fixed ? nbatch : W;  // bucket sets
-  const uint32_t nbt = (uint32_t)WB * NB;
-  const size_t total = n * (size_t)W * nbatch;
-  if (total >= 0x80000000ull) return hipErrorInvalidValue;  // u32 positions in the sorted array
+bool msm_plan(size_t n, int c, int W, int fixed, int nbatch, uint32_t item_len, MsmPlan* out) {
+  if (c < 1 || c > 31 || W < 1 || W > 255) return false;
+  if (nbatch < 1 || nbatch > MSM_MAX_BATCH || (!fixed && nbatch != 1)) return false;
+  MsmPlan p = {};
+  p.c = (uint32_t)c;
+  p.W = (uint32_t)W;
+  p.fixed = fixed ? 1 : 0;
+  p.nbatch = (uint32_t)nbatch;
+  const uint32_t NB = p.NB = 1u << (c - 1);
+  const uint32_t WB = p.WB = (uint32_t)(fixed ? nbatch : W);  // bucket sets
+  if (WB > (uint32_t)MSM_SETS_MAX) return false;
+  if (n >= 0x80000000ull) return false;
+  const uint64_t total = p.total = (uint64_t)n * W * nbatch;
+  if (total >= 0x80000000ull) return false;  // u32 positions in the sorted array
+  // bucket partition geometry: keys < nbt, fine bits fb, coarse bins nbt >> fb.  Fine bits
+  // (the fine pass's fan-out per tile): 10 -- 2x the coarse bins of 11 but half the
+  // per-tile key runs; interleaved on one box the k = 22 proof took 86.5-86.8 ms vs
+  // 86.8-87.3 ms at 11 (8, 9: slower coarse pass)
+  const uint64_t nbt = (uint64_t)WB * NB;
+  int key_bits = 1;
+  while ((1ull << key_bits) < nbt) key_bits++;
+  int fb = key_bits < 10 ? key_bits : 10;
+  while (fb < FB_MAX && ((nbt + (1ull << fb) - 1) >> fb) > COARSE_MAX) fb++;
+  if (((nbt + (1ull << fb) - 1) >> fb) > COARSE_MAX) return false;
+  p.nbt = (uint32_t)nbt;
+  p.fb = (uint32_t)fb;
+  p.ncoarse = (uint32_t)((nbt + (1ull << fb) - 1) >> fb);
+  p.kblocks = (p.nbt + 1023) / 1024;
+  p.staged = total < (uint64_t)H2G_FSTAGE_MAX;
   // buckets most windows can reach (fixed-base: 2^(base width - 1) of the balanced widths)
-  const size_t nb_eff = (size_t)WB << ((fixed ? 255 / W : c) - 1);
+  p.nb_eff = (uint64_t)WB << ((fixed ? 255 / W : c) - 1);
   // the host's chunk length; the device may pick a shorter one once the entries are
   // counted (msm_chunk_len_dev), so everything chunk-sized takes the larger count
-  const uint32_t L = item_len > 0 ? item_len : msm_chunk_len(total, nb_eff);
-  const MsmChunkRule rule{L, item_len > 0 ? 0u : 1u, (uint64_t)total, (uint64_t)nb_eff};
-  const size_t nchunks = msm_chunk_cap(rule);
-  const uint32_t m1 = (NB + RG - 1) / RG;
-  const bool red_q4 = (size_t)m1 * WB <= RED_Q4_MAX;
-  const uint32_t nblk = red_q4 ? (m1 + Q4_GROUPS - 1) / Q4_GROUPS : (m1 + MSM_THREADS - 1) / MSM_THREADS;
+  p.L = item_len > 0 ? item_len : msm_chunk_len(total, p.nb_eff);
+  p.adapt = item_len > 0 ? 0u : 1u;
+  const size_t nchunks = p.nchunks = msm_chunk_cap(msm_chunk_rule(p));
+  p.fixup_q = p.nbt <= FIXUP_Q4_MAX ? 4 : 1;
   // bit planes.  Small sets (<= 2^18 buckets over all sets, e.g. the 2^16 of a 2^19-point
   // slab): quad-cooperative, 256 groups per block, and the fewest buckets per group (rgp)
   // that keep the groups within 2^16 (4 waves per SIMD) -- latency-bound, the reduction
@@ -825,8 +751,8 @@ static hipError_t msm_pipeline(const MsmScalarList& list, int nbatch, const G1Af
   // 256 groups left 4 waves per SIMD on few CUs (2^14 buckets: 64 CUs, ~13 us per level);
   // 4x the blocks spread the same levels over the chip.  The block index then needs 2 more
   // bits (<= RPK_MAX): at most 32768 groups per set.
-  int rgp = 8, plane_q = 4, plane_lb = 8;
-  if ((size_t)NB * WB <= (1u << 18)) {
+  uint32_t rgp = 8, plane_q = 4, plane_lb = 8;
+  if (nbt <= (1u << 18)) {
     plane_lb = kSmallLB;
     for (rgp = 1; rgp < 8; rgp *= 2) {
       const size_t g = (NB + rgp - 1) / rgp;
@@ -838,174 +764,155 @@ static hipError_t msm_pipeline(const MsmScalarList& list, int nbatch, const G1Af
   }
   const uint32_t m1p = (NB + rgp - 1) / rgp;                         // plane groups per set
   const uint32_t nblk_p = (m1p + (1u << plane_lb) - 1) >> plane_lb;  // plane kernels' blocks
+  // the rscale scheme's groups of RG buckets per set, and its blocks of 256 groups
+  const uint32_t m1 = (NB + RG - 1) / RG;
+  const uint32_t nblk = (m1 + MSM_THREADS - 1) / MSM_THREADS;
   // bit planes unless the block index needs more than RPK_MAX bits (sets of > 2^17
-  // groups, e.g. c = 22): those keep the rscale scheme
-  const bool red_plane = nblk_p <= (1u << RPK_MAX);
-  // grow-only workspace: MSMs of slightly different shapes (e.g. n and n - 1 points, so
-  // another chunk length) reuse it instead of reallocating (~2 ms of host stall each)
-  struct Need {
-    void** p;
-    size_t bytes;
-  };
+  // groups: c >= 22, where m1 >= 2^18): those keep the rscale scheme
+  p.red_plane = nblk_p <= (1u << RPK_MAX);
+  if (p.red_plane) {
+    p.plane_q = plane_q;
+    p.plane_lb = plane_lb;
+    p.rgp = rgp;
+    while ((1u << p.e0) < rgp) p.e0++;
+    p.m1p = m1p;
+    p.nblk_p = nblk_p;
+  } else {
+    p.m1 = m1;
+    p.nblk = nblk;
+  }
+  // `red` is sized for the larger of its two layouts, whichever runs.  Its S/R/P term counts
+  // block sums per 64 groups while all sets have at most 32768 groups -- the blocks of quad
+  // group kernels that such sets took before the bit planes -- and is kept so that no
+  // workspace changes size (those sets take the planes)
+  const uint32_t nblk_sized = (size_t)m1 * WB <= 32768 ? (m1 + 63) / 64 : nblk;
   const size_t icap = msm_big_items_cap(nchunks), mcap = msm_big_multi_cap(nchunks);
-  // bucket partition geometry: keys < nbt, fine bits fb, coarse bins nbt >> fb.  Fine bits
-  // (the fine pass's fan-out per tile): 10 -- 2x the coarse bins of 11 but half the
-  // per-tile key runs; interleaved on one box the k = 22 proof took 86.5-86.8 ms vs
-  // 86.8-87.3 ms at 11 (8, 9: slower coarse pass)
-  int key_bits = 1;
-  while ((1ull << key_bits) < (uint64_t)nbt) key_bits++;
-  int fb = key_bits < 10 ? key_bits : 10;
-  while (fb < FB_MAX && (((uint64_t)nbt + (1ull << fb) - 1) >> fb) > COARSE_MAX) fb++;
-  // ent (the coarse-binned entries) is dead once the partition has run: it then holds the
-  // accumulation's whole buckets (raw F29) until the fixup converts them
-  const size_t whole_bytes = (size_t)nbt * sizeof(AccPoint);
-  const Need need[10] = {{&ws->ent, std::max(total * 8, whole_bytes)},
-                         {&ws->vals_out, total * 4},
-                         {&ws->item_bucket, icap * sizeof(MsmBigItem)},    // big-bucket items
-                         {&ws->partials, 2 * nchunks * sizeof(AccPoint)},  // boundary slots
-                         {&ws->buckets, (size_t)nbt * sizeof(RedPoint)},
-                         {&ws->segs, std::max<size_t>((size_t)2 * m1 + nblk, 10 * (size_t)nblk_p + 32) * WB *
-                                         sizeof(RedPoint)},
-                         {&ws->windows, (size_t)(W > WB ? W : WB) * sizeof(G1xyzz)},
-                         // [0] items, [1] multi-item buckets, [4 ..] the accumulation's repair list
-                         {&ws->result, 16 + 4 * (1 + (size_t)MSM_REPAIR_CAP)},
-                         {&ws->item_off, mcap * sizeof(uint4)},          // multi-item buckets
-                         {&ws->total_items, icap * sizeof(RedPoint)}};     // items' partial sums
-  for (int b = 0; b < 10; b++)
-    if (need[b].bytes > ws->cap[b]) {
-      H2G_TRY(grow(need[b].p, need[b].bytes));
-      ws->cap[b] = need[b].bytes;
-    }
+  MsmBytes& b = p.bytes;
+  b.ent = std::max<uint64_t>(total * 8, nbt * sizeof(AccPoint));  // entries, then whole buckets
+  b.vals = total * 4;
+  b.items = icap * sizeof(MsmBigItem);
+  b.bnd = 2 * nchunks * sizeof(AccPoint);
+  b.buckets = nbt * sizeof(RedPoint);
+  b.red = std::max<uint64_t>(2 * (uint64_t)m1 + nblk_sized, 10 * (uint64_t)nblk_p + 32) * WB * sizeof(RedPoint);
+  b.windows = (uint64_t)(p.W > WB ? p.W : WB) * sizeof(G1xyzz);
+  b.counters = 16 + 4 * (1 + (uint64_t)MSM_REPAIR_CAP);
+  b.multi = mcap * sizeof(uint4);
+  b.item_sums = icap * sizeof(RedPoint);
+  p.scratch_words = msm_scratch(nullptr, p.nbt).words;
+  *out = p;
+  return true;
+}
+
+// grow-only (MsmBuf): a buffer already large enough is kept
+static hipError_t ensure(MsmBuf& b, size_t bytes) {
+  if (bytes <= b.cap) return hipSuccess;
+  if (b.p) (void)hipFree(b.p);
+  b.p = nullptr;
+  b.cap = 0;
+  H2G_TRY(hipMalloc(&b.p, bytes));
+  b.cap = bytes;
+  return hipSuccess;
+}
+
+static hipError_t msm_ensure(MsmWorkspace* ws, const MsmPlan& pl, hipStream_t st) {
+  const MsmBytes& b = pl.bytes;
+  H2G_TRY(ensure(ws->ent, b.ent));
+  H2G_TRY(ensure(ws->vals, b.vals));
+  H2G_TRY(ensure(ws->items, b.items));
+  H2G_TRY(ensure(ws->bnd, b.bnd));
+  H2G_TRY(ensure(ws->buckets, b.buckets));
+  H2G_TRY(ensure(ws->red, b.red));
+  H2G_TRY(ensure(ws->windows, b.windows));
+  H2G_TRY(ensure(ws->counters, b.counters));
+  H2G_TRY(ensure(ws->multi, b.multi));
+  H2G_TRY(ensure(ws->item_sums, b.item_sums));
+  if (pl.nbt > ws->kcap) {  // a new layout: every count starts at zero again
+    H2G_TRY(ensure(ws->scratch, pl.scratch_words * 4));
+    H2G_TRY(hipMemsetAsync(ws->scratch.p, 0, pl.scratch_words * 4, st));
+    ws->kcap = pl.nbt;
+  }
+  return hipSuccess;
+}
+
+void msm_free(MsmWorkspace* ws) {
+  for (MsmBuf* b : {&ws->ent, &ws->vals, &ws->items, &ws->bnd, &ws->buckets, &ws->red, &ws->windows, &ws->counters,
+                    &ws->multi, &ws->item_sums, &ws->scratch}) {
+    if (b->p) (void)hipFree(b->p);
+    *b = MsmBuf{};
+  }
+  ws->kcap = 0;
+}
+
+// step 5: the buckets' weighted sums per set into windows[], by the plan's scheme
+static void msm_reduce(const MsmPlan& pl, const RedPoint* buckets, RedPoint* red, uint32_t* rdone, G1xyzz* windows,
+                       hipStream_t st) {
+  const unsigned T = MSM_THREADS;
+  if (pl.red_plane) {  // bit planes (6a')
+    RedPoint* planes = red;
+    RedPoint* mid = planes + (size_t)(pl.plane_lb + 2) * pl.WB * pl.nblk_p;
+    // the instance the plan names by (plane_q, rgp)
+    void (*rgroup)(const RedPoint*, uint32_t, uint32_t, uint32_t, RedPoint*) =
+        pl.plane_q == 1 ? msm_rgroup_plane_kernel<1, 8, kLargeRGP>
+        : pl.rgp == 1   ? msm_rgroup_plane_kernel<4, kSmallLB, 1>
+        : pl.rgp == 2   ? msm_rgroup_plane_kernel<4, kSmallLB, 2>
+        : pl.rgp == 4   ? msm_rgroup_plane_kernel<4, kSmallLB, 4>
+                        : msm_rgroup_plane_kernel<4, kSmallLB, 8>;
+    hipLaunchKernelGGL(rgroup, dim3(pl.nblk_p, pl.WB), dim3(pl.plane_q << pl.plane_lb), 0, st, buckets, pl.NB, pl.m1p,
+                       pl.nblk_p, planes);
+    hipLaunchKernelGGL(msm_rplane_mid_kernel, dim3(pl.plane_lb + 2, pl.WB), dim3(H2G_RPM_THREADS), 0, st,
+                       (const RedPoint*)planes, pl.nblk_p, (int)pl.plane_lb, (int)pl.e0, mid, rdone, windows);
+  } else {  // rscale scheme (6a): group sums, group weights, block sums
+    RedPoint *rS = red, *rR = rS + (size_t)pl.WB * pl.m1, *rP = rR + (size_t)pl.WB * pl.m1;
+    hipLaunchKernelGGL(msm_rgroup_kernel, dim3((pl.m1 + T - 1) / T, pl.WB), dim3(T), 0, st, buckets, pl.NB, pl.m1, rS,
+                       rR);
+    hipLaunchKernelGGL(msm_rscale_kernel, dim3(pl.nblk, pl.WB), dim3(T), 0, st, (const RedPoint*)rS,
+                       (const RedPoint*)rR, pl.m1, rP, pl.nblk);
+    hipLaunchKernelGGL(msm_rfinal_q4_kernel, dim3(pl.WB), dim3(T), 0, st, (const RedPoint*)rP, pl.nblk, windows);
+  }
+}
+
+static hipError_t msm_pipeline(const MsmScalarList& list, int nbatch, const G1Affine* d_bases, size_t n, int c,
+                               int W, int fixed, size_t stride, MsmWorkspace* ws, uint32_t item_len, G1Affine* d_out,
+                               hipStream_t st, MsmPhaseEvents* prof) {
+#define H2G_PHASE(i) \
+  if (prof) H2G_TRY(hipEventRecord(prof->ev[i], st))
+  MsmPlan pl;
+  if (!msm_plan(n, c, W, fixed, nbatch, item_len, &pl)) return hipErrorInvalidValue;
+  H2G_TRY(msm_ensure(ws, pl, st));
   ws->last_c = c;
-  ws->last_W = WB;
-  uint32_t* vals_out = (uint32_t*)ws->vals_out;
-  uint32_t* counters = (uint32_t*)ws->result;
-  MsmBigItem* items = (MsmBigItem*)ws->item_bucket;
-  uint4* multi = (uint4*)ws->item_off;
-  RedPoint* ipart = (RedPoint*)ws->total_items;
-  RedPoint* buckets = (RedPoint*)ws->buckets;
-  AccPoint* bnd = (AccPoint*)ws->partials;
-  AccPoint* whole = (AccPoint*)ws->ent;  // the accumulation's whole buckets
-  RedPoint* rS = (RedPoint*)ws->segs;  // rscale scheme: group sums, group weights, block sums
-  RedPoint* rR = rS + (size_t)WB * m1;
-  RedPoint* rP = rR + (size_t)WB * m1;
+  ws->last_W = (int)pl.WB;
+  const MsmScratch s = msm_scratch((uint32_t*)ws->scratch.p, ws->kcap);
+  uint32_t* vals = (uint32_t*)ws->vals.p;
+  uint32_t* counters = (uint32_t*)ws->counters.p;
+  MsmBigItem* items = (MsmBigItem*)ws->items.p;
+  uint4* multi = (uint4*)ws->multi.p;
+  RedPoint* item_sums = (RedPoint*)ws->item_sums.p;
+  RedPoint* buckets = (RedPoint*)ws->buckets.p;
+  AccPoint* bnd = (AccPoint*)ws->bnd.p;
+  AccPoint* whole = (AccPoint*)ws->ent.p;  // the accumulation's whole buckets (ent's second use)
+  G1xyzz* windows = (G1xyzz*)ws->windows.p;
+  const unsigned T = MSM_THREADS;
 
-  const uint32_t ncoarse = (uint32_t)(((uint64_t)nbt + (1ull << fb) - 1) >> fb);
-  if (ncoarse > COARSE_MAX) return hipErrorInvalidValue;
-  const uint32_t kblocks = (nbt + 1023) / 1024;
-  constexpr int RDONE_MAX = 256;  // bucket sets: W <= 128 windows (c >= 2), or nbatch <= MSM_MAX_BATCH
-  if (WB > RDONE_MAX) return hipErrorInvalidValue;
-  // scratch (u32), laid out for a per-key capacity kcap >= nbt so that the counts stay at
-  // fixed places: ccount | coff | ccursor | total | rdone | kbsum | kboff | kcount | koff
-  // (kcap + 1) | kcursor.  Zeroed when allocated; the scans zero ccount / kcount after
-  // reading them, so no MSM needs a fill.
-  if ((size_t)nbt > ws->sort_kcap) {
-    const size_t kcap = nbt, kbmax = (kcap + 1023) / 1024;
-    const size_t words = 3 * (size_t)COARSE_MAX + 16 + RDONE_MAX + 2 * kbmax + 3 * kcap + 1;
-    H2G_TRY(grow(&ws->sort_tmp, words * 4));
-    H2G_TRY(hipMemsetAsync(ws->sort_tmp, 0, words * 4, st));
-    ws->sort_tmp_bytes = words * 4;
-    ws->sort_kcap = kcap;
-  }
-  const size_t kcap = ws->sort_kcap, kbmax = (kcap + 1023) / 1024;
-  uint32_t* ccount = (uint32_t*)ws->sort_tmp;
-  uint32_t* coff = ccount + COARSE_MAX;
-  uint32_t* ccursor = coff + COARSE_MAX;
-  uint32_t* d_total = ccursor + COARSE_MAX;
-  uint32_t* rdone = d_total + 16;  // plane reduction: finished blocks per set
-  uint32_t* kbsum = rdone + RDONE_MAX;
-  uint32_t* kboff = kbsum + kbmax;
-  uint32_t* kcount = kboff + kbmax;
-  uint32_t* koff = kcount + kcap;
-  uint32_t* kcursor = koff + kcap + 1;
-
-  const int T = MSM_THREADS;
   H2G_PHASE(0);
-  {  // rounds 1 and 2 (msm_part.hip); phase event 1 between them
-    MsmPartArgs pa;
-    pa.list = list;
-    pa.nbatch = nbatch;
-    pa.n = n;
-    pa.c = c;
-    pa.W = W;
-    pa.NB = NB;
-    pa.fixed = fixed;
-    pa.stride = stride;
-    pa.total = total;
-    pa.fb = fb;
-    pa.ncoarse = ncoarse;
-    pa.nbt = nbt;
-    pa.kblocks = kblocks;
-    pa.ccount = ccount;
-    pa.coff = coff;
-    pa.ccursor = ccursor;
-    pa.d_total = d_total;
-    pa.kbsum = kbsum;
-    pa.kboff = kboff;
-    pa.kcount = kcount;
-    pa.koff = koff;
-    pa.kcursor = kcursor;
-    pa.ent = (uint64_t*)ws->ent;
-    pa.out = vals_out;
-    pa.z = MsmZero{counters, rdone, (uint32_t)WB};
-    pa.rule = rule;
-    H2G_TRY(msm_partition(pa, st, prof));
-  }
+  // steps 1 and 2, rounds 1 and 2 of the partition (msm_part.hip); phase event 1 between them
+  H2G_TRY(msm_partition(MsmPartArgs{list, n, stride, &pl, s, (uint64_t*)ws->ent.p, vals, counters}, st, prof));
   H2G_PHASE(2);
   H2G_PHASE(3);
-  H2G_TRY(msm_accumulate(d_bases, vals_out, koff, nbt, d_total, nchunks, whole, bnd, counters + 4, st));
+  H2G_TRY(msm_accumulate(d_bases, vals, s.koff, pl.nbt, s.d_total, pl.nchunks, whole, bnd, counters + 4, st));
   H2G_PHASE(4);
-  if (nbt <= FIXUP_Q4_MAX)
-    hipLaunchKernelGGL(msm_fixup_kernel<4>, dim3((unsigned)(((size_t)nbt * 4 + T - 1) / T)), dim3(T), 0, st,
-                       (const AccPoint*)bnd, (const uint32_t*)koff, nbt, (const uint32_t*)d_total,
-                       (const AccPoint*)whole, buckets, items, multi, counters);
-  else
-    hipLaunchKernelGGL(msm_fixup_kernel<1>, dim3((nbt + T - 1) / T), dim3(T), 0, st, (const AccPoint*)bnd,
-                       (const uint32_t*)koff, nbt, (const uint32_t*)d_total, (const AccPoint*)whole, buckets, items,
-                       multi, counters);
+  const auto fixup = pl.fixup_q == 4 ? msm_fixup_kernel<4> : msm_fixup_kernel<1>;
+  hipLaunchKernelGGL(fixup, dim3((unsigned)(((size_t)pl.nbt * pl.fixup_q + T - 1) / T)), dim3(T), 0, st,
+                     (const AccPoint*)bnd, (const uint32_t*)s.koff, pl.nbt, (const uint32_t*)s.d_total,
+                     (const AccPoint*)whole, buckets, items, multi, counters);
   hipLaunchKernelGGL(msm_big_item_kernel, dim3(MSM_BIG_BLOCKS), dim3(T), 0, st, (const AccPoint*)bnd,
-                     (const uint32_t*)koff, (const uint32_t*)d_total, (const MsmBigItem*)items,
-                     (const uint32_t*)counters, ipart, buckets);
+                     (const uint32_t*)s.koff, (const uint32_t*)s.d_total, (const MsmBigItem*)items,
+                     (const uint32_t*)counters, item_sums, buckets);
   hipLaunchKernelGGL(msm_big_combine_kernel, dim3(MSM_BIG_BLOCKS / 4), dim3(T), 0, st, (const uint4*)multi,
-                     (const uint32_t*)counters, (const RedPoint*)ipart, buckets);
+                     (const uint32_t*)counters, (const RedPoint*)item_sums, buckets);
   H2G_PHASE(5);
-  if (red_plane) {  // bit planes (6a')
-    RedPoint* planes = (RedPoint*)ws->segs;
-    RedPoint* mid = planes + (size_t)(plane_lb + 2) * WB * nblk_p;
-    int e0 = 0;
-    while ((1 << e0) < rgp) e0++;
-    const dim3 pg(nblk_p, (unsigned)WB), pb((unsigned)(plane_q << plane_lb));
-    const RedPoint* bk = buckets;
-    if (plane_q == 1)
-      hipLaunchKernelGGL((msm_rgroup_plane_kernel<1, 8, kLargeRGP>), pg, pb, 0, st, bk, NB, m1p, nblk_p, planes);
-    else if (rgp == 1)
-      hipLaunchKernelGGL((msm_rgroup_plane_kernel<4, kSmallLB, 1>), pg, pb, 0, st, bk, NB, m1p, nblk_p, planes);
-    else if (rgp == 2)
-      hipLaunchKernelGGL((msm_rgroup_plane_kernel<4, kSmallLB, 2>), pg, pb, 0, st, bk, NB, m1p, nblk_p, planes);
-    else if (rgp == 4)
-      hipLaunchKernelGGL((msm_rgroup_plane_kernel<4, kSmallLB, 4>), pg, pb, 0, st, bk, NB, m1p, nblk_p, planes);
-    else
-      hipLaunchKernelGGL((msm_rgroup_plane_kernel<4, kSmallLB, 8>), pg, pb, 0, st, bk, NB, m1p, nblk_p, planes);
-    hipLaunchKernelGGL(msm_rplane_mid_kernel, dim3((unsigned)plane_lb + 2, (unsigned)WB), dim3(H2G_RPM_THREADS), 0, st,
-                       (const RedPoint*)planes, nblk_p, plane_lb, e0, mid, rdone, (G1xyzz*)ws->windows);
-  } else {
-    if (red_q4)
-      hipLaunchKernelGGL(msm_rgroup_q4_kernel, dim3((unsigned)(((size_t)m1 * 4 + T - 1) / T), (unsigned)WB),
-                         dim3(T), 0, st, (const RedPoint*)buckets, NB, m1, rS, rR);
-    else
-      hipLaunchKernelGGL(msm_rgroup_kernel, dim3((m1 + T - 1) / T, (unsigned)WB), dim3(T), 0, st,
-                         (const RedPoint*)buckets, NB, m1, rS, rR);
-    if (red_q4)
-      hipLaunchKernelGGL(msm_rscale_q4_kernel, dim3(nblk, (unsigned)WB), dim3(T), 0, st, (const RedPoint*)rS,
-                         (const RedPoint*)rR, m1, rP, nblk);
-    else
-      hipLaunchKernelGGL(msm_rscale_kernel, dim3(nblk, (unsigned)WB), dim3(T), 0, st, (const RedPoint*)rS,
-                         (const RedPoint*)rR, m1, rP, nblk);
-    hipLaunchKernelGGL(msm_rfinal_q4_kernel, dim3((unsigned)WB), dim3(T), 0, st, (const RedPoint*)rP, nblk,
-                       (G1xyzz*)ws->windows);
-  }
+  msm_reduce(pl, buckets, (RedPoint*)ws->red.p, s.rdone, windows, st);
   if (d_out && nbatch == 1)
-    hipLaunchKernelGGL(msm_final_kernel, dim3(1), dim3(64), 0, st, (const G1xyzz*)ws->windows, WB, c, d_out);
+    hipLaunchKernelGGL(msm_final_kernel, dim3(1), dim3(64), 0, st, (const G1xyzz*)windows, (int)pl.WB, c, d_out);
   H2G_TRY(hipGetLastError());
   H2G_PHASE(6);
 #undef H2G_PHASE

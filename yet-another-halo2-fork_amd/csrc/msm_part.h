@@ -59,6 +59,9 @@ struct MsmChunkRule {
   uint64_t bound;   // entry bound n W nbatch
   uint64_t nb_eff;  // buckets the windows can reach (the host rule's quarter-bucket floor)
 };
+__host__ __forceinline__ MsmChunkRule msm_chunk_rule(const MsmPlan& pl) {
+  return MsmChunkRule{pl.L, pl.adapt, pl.total, pl.nb_eff};
+}
 static constexpr int MSM_ADAPT_LG = 18;  // threads the device choice aims for (2^18)
 __host__ __device__ __forceinline__ uint32_t msm_chunk_len_dev(uint64_t actual, const MsmChunkRule& r) {
   if (!r.adapt || 2 * actual > r.bound) return r.Lh;
@@ -78,34 +81,70 @@ __host__ __forceinline__ size_t msm_chunk_cap(const MsmChunkRule& r) {
   return host > dev ? host : dev;
 }
 
+// The partition's second round takes its LDS-staged form (msm_part.hip) for MSMs below
+// this many entries, the slabs of sharded proofs: 2^19 points 0.108 -> 0.084 ms, 2^21
+// 0.356 -> 0.30 ms; at 2^22 no faster, 0.61 vs 0.60 ms.  msm_plan decides (MsmPlan::staged).
+#ifndef H2G_FSTAGE_MAX
+#define H2G_FSTAGE_MAX (1ull << 25)
+#endif
+
+// The u32 scratch of one workspace, laid out for a per-key capacity kcap >= nbt so that the
+// counts stay at fixed places while smaller MSMs reuse it.  Zeroed when allocated; the
+// scans zero ccount / kcount after reading them, so no MSM needs a fill.
+static constexpr int MSM_SETS_MAX = 256;  // bucket sets: W <= 128 windows (c >= 2), or nbatch <= MSM_MAX_BATCH
+struct MsmScratch {
+  uint32_t *ccount, *coff, *ccursor;  // [COARSE_MAX] each: coarse counts, offsets, cursors
+  uint32_t* d_total;                  // [16]: [0] the entries, [1] the accumulation's chunk length
+  uint32_t* rdone;                    // [MSM_SETS_MAX] plane reduction: finished blocks per set
+  uint32_t *kbsum, *kboff;            // [ceil(kcap / 1024)] each: the key scan's block sums, offsets
+  uint32_t *kcount, *koff, *kcursor;  // [kcap], [kcap + 1], [kcap]: per-key counts, run starts, cursors
+  size_t words;                       // the whole layout
+};
+// base == nullptr: only `words` means anything
+__host__ inline MsmScratch msm_scratch(uint32_t* base, size_t kcap) {
+  const size_t kb = (kcap + 1023) / 1024;
+  MsmScratch s;
+  s.words = 0;
+  auto take = [&](size_t w) {
+    uint32_t* p = base ? base + s.words : nullptr;
+    s.words += w;
+    return p;
+  };
+  s.ccount = take(COARSE_MAX);
+  s.coff = take(COARSE_MAX);
+  s.ccursor = take(COARSE_MAX);
+  s.d_total = take(16);
+  s.rdone = take(MSM_SETS_MAX);
+  s.kbsum = take(kb);
+  s.kboff = take(kb);
+  s.kcount = take(kcap);
+  s.koff = take(kcap + 1);
+  s.kcursor = take(kcap);
+  return s;
+}
+
 // One partition of the MSM pipeline's entries: round 1 (coarse bins straight from the
 // scalars, into ent), phase event 1, round 2 (keys inside the bins: the values in bucket
-// order into out, koff[k] = the first position of key k's run, koff[nbt] = the entry
-// count).  The scratch arrays are msm_pipeline's (zero counts on entry, left zero).
+// order into out, s.koff[k] = the first position of key k's run, s.koff[nbt] = the entry
+// count, s.d_total[1] = the accumulation's chunk length).  The scratch counts are zero on
+// entry and left zero; `counters` ([0], [1], [4]) and s.rdone are zeroed for the later phases.
 struct MsmPartArgs {
   MsmScalarList list;
-  int nbatch;
-  size_t n;
-  int c, W;
-  uint32_t NB;
-  int fixed;
-  size_t stride;
-  size_t total;  // upper bound of the entries (n W nbatch)
-  int fb;
-  uint32_t ncoarse, nbt, kblocks;
-  uint32_t *ccount, *coff, *ccursor, *d_total, *kbsum, *kboff, *kcount, *koff, *kcursor;
+  size_t n, stride;
+  const MsmPlan* plan;
+  MsmScratch s;
   uint64_t* ent;
   uint32_t* out;
-  MsmZero z;
-  MsmChunkRule rule;  // d_total[1] = the accumulation's chunk length
+  uint32_t* counters;
 };
 hipError_t msm_partition(const MsmPartArgs& a, hipStream_t st, MsmPhaseEvents* prof);
 
 // The accumulation's arithmetic is F29 (f29.h: 9 x 29-bit limbs, no carry ops in the
 // products); its buckets and boundary slots are raw G1xyzz29 accumulators (144 B),
-// converted to canonical G1xyzz by the fixup.
+// which the fixup reduces into f29.h's back-end class.  One type, two names for the two
+// coordinate ranges: what the accumulation writes, and what the fixup and reduction add.
 using AccPoint = G1xyzz29;
-using RedPoint = G1xyzz29;  // the fixup's and the reduction's points (f29.h's back-end class)
+using RedPoint = G1xyzz29;
 
 // raw 16-B moves of the accumulators (G1xyzz29 is 9 x 16 B)
 __device__ __forceinline__ void st_acc(G1xyzz29* dst, const G1xyzz29& v) {
@@ -128,7 +167,6 @@ __device__ __forceinline__ G1xyzz29 ld_acc(const G1xyzz29* src) {
   }
   return v;
 }
-__device__ __forceinline__ G1xyzz acc_to_xyzz(const G1xyzz29& v) { return xyzz_from29(v); }
 
 // step 3 of the pipeline (msm_acc.hip): XYZZ accumulation of the bucket-sorted values in
 // chunks of L = d_total[1] (d_total[0]: the entries), one thread per chunk (a grid for

@@ -267,17 +267,13 @@ msm_fine_scatter_kernel(const uint64_t* __restrict__ in, const uint32_t* __restr
     if (rk[k] != ~0u) out[base[(uint32_t)(ent[k] >> 32) & (nf - 1)] + rk[k]] = (uint32_t)ent[k];
 }
 
-// round 2, staged form (MSMs below 2^25 entries, the slabs of sharded proofs: 2^19
-// points 0.108 -> 0.084 ms, 2^21 0.356 -> 0.30 ms; at 2^22 no faster, 0.61 vs 0.60 ms):
+// round 2, staged form (MSMs below H2G_FSTAGE_MAX entries, msm_part.h):
 // tiles of SW_T threads x SW_PER entries (8192) whose keys inside a local window of SW_LK
 // keys (the tile's first coarse bin and the next) are counted and ranked in LDS, reserved
 // with one global atomic per (tile, key), then written through an LDS copy of the tile in
 // key order -- a wave's stores are runs of each key's share of the tile instead of 64
 // scattered writes, and the per-key global atomics drop 4x with the larger tile.  Keys
 // outside the window (tiles straddling more than two bins) take a global atomic each.
-#ifndef H2G_FSTAGE_MAX
-#define H2G_FSTAGE_MAX (1ull << 25)
-#endif
 static constexpr int SW_T = 512;
 static constexpr int SW_PER = 16;
 static constexpr uint32_t SW_TILE = (uint32_t)SW_T * SW_PER;
@@ -390,43 +386,47 @@ msm_fine_scatter_staged_kernel(const uint64_t* __restrict__ in, const uint32_t* 
 }
 
 hipError_t msm_partition(const MsmPartArgs& a, hipStream_t st, MsmPhaseEvents* prof) {
-  const bool fstage = a.total < (uint64_t)H2G_FSTAGE_MAX;  // the staged fine pass (above)
+  const MsmPlan& pl = *a.plan;
+  const MsmScratch& s = a.s;
   {  // round 1: coarse bins straight from the scalars
-    const dim3 g((unsigned)((a.n + PT - 1) / PT), (unsigned)a.nbatch, (unsigned)((a.W + PWG - 1) / PWG));
-    hipLaunchKernelGGL(msm_coarse_hist_kernel, g, dim3(PT), 0, st, a.list, a.n, a.c, a.W, a.NB, a.fixed, a.stride,
-                       a.fb, a.ncoarse, a.ccount, a.z);
-    hipLaunchKernelGGL(msm_scan_kernel, dim3(1), dim3(1024), 0, st, a.ccount, a.ncoarse, a.coff, a.ccursor,
-                       a.d_total, true);
-    hipLaunchKernelGGL(msm_coarse_scatter_kernel, g, dim3(PT), 0, st, a.list, a.n, a.c, a.W, a.NB, a.fixed, a.stride,
-                       a.fb, a.ncoarse, a.ccursor, a.ent);
+    const dim3 g((unsigned)((a.n + PT - 1) / PT), pl.nbatch, (pl.W + PWG - 1) / PWG);
+    const MsmZero z{a.counters, s.rdone, pl.WB};
+    hipLaunchKernelGGL(msm_coarse_hist_kernel, g, dim3(PT), 0, st, a.list, a.n, (int)pl.c, (int)pl.W, pl.NB,
+                       (int)pl.fixed, a.stride, (int)pl.fb, pl.ncoarse, s.ccount, z);
+    hipLaunchKernelGGL(msm_scan_kernel, dim3(1), dim3(1024), 0, st, s.ccount, pl.ncoarse, s.coff, s.ccursor,
+                       s.d_total, true);
+    hipLaunchKernelGGL(msm_coarse_scatter_kernel, g, dim3(PT), 0, st, a.list, a.n, (int)pl.c, (int)pl.W, pl.NB,
+                       (int)pl.fixed, a.stride, (int)pl.fb, pl.ncoarse, s.ccursor, a.ent);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
   if (prof) {
     hipError_t e = hipEventRecord(prof->ev[1], st);
-    if (e == hipSuccess && prof->entries) e = hipMemcpyAsync(prof->entries, a.d_total, 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && prof->entries) e = hipMemcpyAsync(prof->entries, s.d_total, 4, hipMemcpyDeviceToHost, st);
     if (e != hipSuccess) return e;
   }
   {  // round 2: keys inside the coarse bins
-    const unsigned tiles = (unsigned)((a.total + FTILE - 1) / FTILE);
-    const unsigned stiles = (unsigned)((a.total + SW_TILE - 1) / SW_TILE);
-    if (fstage)
-      hipLaunchKernelGGL(msm_fine_hist_staged_kernel, dim3(stiles), dim3(SW_T), 0, st, (const uint64_t*)a.ent,
-                         (const uint32_t*)a.d_total, a.fb, stiles, a.kcount);
+    const int fb = (int)pl.fb;
+    const uint64_t* ent = a.ent;
+    const uint32_t* d_total = s.d_total;
+    const unsigned tiles = (unsigned)((pl.total + FTILE - 1) / FTILE);
+    const unsigned stiles = (unsigned)((pl.total + SW_TILE - 1) / SW_TILE);
+    if (pl.staged)
+      hipLaunchKernelGGL(msm_fine_hist_staged_kernel, dim3(stiles), dim3(SW_T), 0, st, ent, d_total, fb, stiles,
+                         s.kcount);
     else
-      hipLaunchKernelGGL(msm_fine_hist_kernel, dim3(tiles), dim3(FT), 0, st, (const uint64_t*)a.ent,
-                         (const uint32_t*)a.d_total, a.fb, tiles, a.kcount);
-    hipLaunchKernelGGL(msm_scan_block_kernel, dim3(a.kblocks), dim3(1024), 0, st, a.kcount, a.nbt, a.koff, a.kbsum);
-    hipLaunchKernelGGL(msm_scan_kernel, dim3(1), dim3(1024), 0, st, a.kbsum, a.kblocks, a.kboff, (uint32_t*)nullptr,
+      hipLaunchKernelGGL(msm_fine_hist_kernel, dim3(tiles), dim3(FT), 0, st, ent, d_total, fb, tiles, s.kcount);
+    hipLaunchKernelGGL(msm_scan_block_kernel, dim3(pl.kblocks), dim3(1024), 0, st, s.kcount, pl.nbt, s.koff, s.kbsum);
+    hipLaunchKernelGGL(msm_scan_kernel, dim3(1), dim3(1024), 0, st, s.kbsum, pl.kblocks, s.kboff, (uint32_t*)nullptr,
                        (uint32_t*)nullptr, false);
-    hipLaunchKernelGGL(msm_scan_add_kernel, dim3(a.kblocks), dim3(1024), 0, st, a.koff, a.nbt,
-                       (const uint32_t*)a.kboff, a.kcursor, a.d_total, a.rule);
-    if (fstage)
-      hipLaunchKernelGGL(msm_fine_scatter_staged_kernel, dim3(stiles), dim3(SW_T), 0, st, (const uint64_t*)a.ent,
-                         (const uint32_t*)a.d_total, a.fb, stiles, a.kcursor, a.out);
+    hipLaunchKernelGGL(msm_scan_add_kernel, dim3(pl.kblocks), dim3(1024), 0, st, s.koff, pl.nbt,
+                       (const uint32_t*)s.kboff, s.kcursor, s.d_total, msm_chunk_rule(pl));
+    if (pl.staged)
+      hipLaunchKernelGGL(msm_fine_scatter_staged_kernel, dim3(stiles), dim3(SW_T), 0, st, ent, d_total, fb, stiles,
+                         s.kcursor, a.out);
     else
-      hipLaunchKernelGGL(msm_fine_scatter_kernel, dim3(tiles), dim3(FT), 0, st, (const uint64_t*)a.ent,
-                         (const uint32_t*)a.d_total, a.fb, tiles, a.kcursor, a.out);
+      hipLaunchKernelGGL(msm_fine_scatter_kernel, dim3(tiles), dim3(FT), 0, st, ent, d_total, fb, tiles, s.kcursor,
+                         a.out);
   }
   return hipGetLastError();
 }

@@ -66,6 +66,7 @@ _SIGS = {
     "h2g_divide_by_vanishing_poly": ([U64, U64P], I32),
     "h2g_divide_by_vanishing_poly_dev": ([U64, VP, VP], I32),
     "h2g_debug_ntt_plan": ([U32, U64, U64, I32, I32, I32, I32, VP], I32),
+    "h2g_debug_msm_plan": ([U64, I32, I32, I32, U32, VP], I32),
     "h2g_fr_op": ([I32, U64P, U64P, U64P, U64P, SZ], I32),
     "h2g_fr_op_dev": ([I32, VP, VP, U64P, VP, SZ, VP], I32),
     "h2g_fr_batch_invert": ([U64P, SZ], I32),
@@ -481,6 +482,28 @@ def debug_ntt_plan(log_n, n_in, out_len=0, count=1, in_twist=False, cus=256, epi
     return {"split": tuple(pl.lg[:pl.passes]), "first": NTT_FIRST[pl.first], "trunc": bool(pl.last_trunc),
             "one": bool(pl.last_one), "cus": pl.cus, "blocks": pl.blocks, "first_grid": pl.first_grid,
             "pgrid": {p: pl.pgrid[p] for p in range(1, pl.passes - 1)}}
+
+
+MSM_BUFFERS = ("ent", "vals", "items", "bnd", "buckets", "red", "windows", "counters", "multi", "item_sums")
+
+
+class MsmPlan(ctypes.Structure):  # h2g_msm_plan
+    _fields_ = ([("total", U64), ("nb_eff", U64), ("nchunks", U64), ("bytes", U64 * 10), ("scratch_words", U64)] +
+                [(f, U32) for f in ("c", "W", "fixed", "nbatch", "WB", "NB", "nbt", "chunk_len", "chunk_adapt", "fb",
+                                    "ncoarse", "kblocks", "staged", "fixup_q", "red_plane", "plane_q", "plane_lb",
+                                    "rgp", "e0", "m1p", "nblk_p", "m1", "nblk", "reserved")])
+
+
+def debug_msm_plan(n, c=0, fixed=False, nbatch=1, item_len=0):
+    """h2g_debug_msm_plan (test seam, host only): what an MSM of n points decides before it
+    allocates or launches -> dict of h2g_msm_plan's fields, `bytes` as {buffer: bytes} over
+    MSM_BUFFERS, and "red": "plane" or "rscale".  c = 0: the library's window choice for n."""
+    pl = MsmPlan()
+    check(lib().h2g_debug_msm_plan(n, c, int(bool(fixed)), nbatch, item_len, ctypes.byref(pl)))
+    d = {f: getattr(pl, f) for f, _ in MsmPlan._fields_ if f not in ("bytes", "reserved")}
+    d["bytes"] = dict(zip(MSM_BUFFERS, pl.bytes))
+    d["red"] = "plane" if pl.red_plane else "rscale"
+    return d
 
 
 # ----------------------------------------------------------------- poly ops
