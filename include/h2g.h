@@ -208,6 +208,37 @@ typedef struct h2g_msm_plan {
   uint32_t reserved;
 } h2g_msm_plan;
 int h2g_debug_msm_plan(uint64_t n, int c, int fixed, int nbatch, uint32_t item_len, h2g_msm_plan* plan);
+/* test seam: the per-launch capacities by which the prover's host loops split wide work, so that
+ * tests can take their shapes from them (cap - 1, cap, cap + 1, 2 cap + 1).  Writes the first
+ * min(max, H2G_LIMIT_COUNT) of them to out, in the order of the enum, and H2G_LIMIT_COUNT to
+ * *count.  Host only: needs no h2g_init. */
+enum {
+  H2G_LIMIT_COPY_COLS = 0,    /* advice columns per copy / column-sum launch (device-resident advice, check_witness) */
+  H2G_LIMIT_PREFIX_DIFF = 1,  /* permuted lookup columns per prefix-difference launch */
+  H2G_LIMIT_COMPRESS_BATCH = 2, /* lookup / shuffle expressions per compression launch */
+  H2G_LIMIT_LOOKUP_KEYS_BATCH = 3, /* columns per sort-key launch */
+  H2G_LIMIT_PERM_COLS = 4,    /* permutation columns per numerator / denominator launch */
+  H2G_LIMIT_LIN_TERMS = 5,    /* terms per linear-combination launch (the multi-open uses one or two fewer) */
+  H2G_LIMIT_NTT_BATCH = 6,    /* transforms per launch */
+  H2G_LIMIT_POLY_INV_BATCH = 7, /* arrays per batched inversion / prefix-product launch */
+  H2G_LIMIT_MSM_BATCH = 8,    /* MSMs per batched pipeline */
+  H2G_LIMIT_MSM_RING = 9,     /* result slots of one block of the asynchronous MSMs' ring (more are added on demand) */
+  H2G_LIMIT_COUNT = 10
+};
+int h2g_debug_limits(int32_t* out, int max, int* count);
+/* test seam: how many commitments of n points the prover batches into one MSM pipeline against
+ * fixed-base windows of table_c bits (1: each goes alone).  Never a batch that
+ * h2g_debug_msm_plan(n, table_c, 1, chunk) refuses.  Host only: needs no h2g_init. */
+int h2g_debug_commit_batch_chunk(int table_c, uint64_t n, int* chunk);
+/* test seam: the prover's commitment schedule on its own.  nb_total MSMs sum_i d_scalars[b][i] *
+ * bases[base_offset + i] (i < n) against a base descriptor's fixed-base windows
+ * (h2g_msm_base_descriptor_dev), launched back to back in ceil(nb_total / chunk) batched
+ * pipelines of up to `chunk` (1..64) MSMs -- chunk = 1: one plain pipeline each, the schedule of
+ * commitments too large to batch -- and collected only after the last launch, as a proof stage
+ * does.  out_affine: nb_total x 8 limbs ((0, 0) for the identity); is_identity: nb_total flags,
+ * or null.  H2G_ERR_ARG, with nothing launched, when a batch is a shape the MSM refuses. */
+int h2g_debug_msm_batches_dev(uint64_t base, size_t base_offset, const void* const* d_scalars, int nb_total,
+                              int chunk, size_t n, uint64_t* out_affine, int32_t* is_identity);
 
 /* ---- Polynomial<F, B> arithmetic (halo2_backend/src/poly.rs:200-276) ---------
  * op: 0 add a+b, 1 sub a-b, 2 mul a*b, 3 scale a*c, 4 sub_const a-c, 5 add_const a+c,

@@ -176,8 +176,10 @@ def test_msm_every_reachable_variant(name, variant_inputs):
     against a table (msm_with_cached_base_dev), the one entry fixed-base MSMs have -- its
     final combine is the host's.  The rscale scheme exists only there: msm_dev refuses c >= 20
     (13 x 2^19 buckets; test_msm_plan_cpu.py::test_first_refused_partition).
-    The batched fixed-base pipeline (more than one bucket set against a table) has no public
-    entry of its own and stays covered by the prover tests, whose commitments run through it."""
+    The batched fixed-base pipeline (more than one bucket set against a table) runs at every
+    variant a batch size selects in tests/test_gpu_msm_batched.py, through its own seam
+    (h2g_debug_msm_batches_dev); circuits wide enough to split a stage's commitments into
+    several batches are in tests/test_gpu_wide_circuits.py."""
     want_plan, shape = MSM_VARIANTS[name]
     n = MSM_VARIANT_N
     pl = h2g.debug_msm_plan(n, **shape)

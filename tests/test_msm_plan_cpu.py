@@ -274,3 +274,56 @@ def test_variable_base_default_window_is_refused_from_2_24_points():
     assert variant(n=1 << 23) == Q1 and h2g.debug_msm_plan(1 << 23)["c"] == 19
     assert variant(n=1 << 24) == REFUSED and variant(n=1 << 24, c=20) == REFUSED
     assert variant(n=1 << 24, c=19) == Q1
+
+
+# ----------------------------------------------------------------------------- the commitment batch
+FIXED_C = dict(zip(range(8, 28), [9, 10, 10, 11, 13, 13, 15, 15, 15, 16, 17, 17, 19, 20, 20, 22, 22, 22, 22, 22]))
+
+
+def test_commit_batch_chunk_rule():
+    """commit_batch_chunk (csrc/commit.cpp): min(64, 2^27 / (W n)) commitments of n points in one
+    pipeline, none batched past 2^25 entries each"""
+    assert h2g.debug_commit_batch_chunk(17, 1 << 18) == (1 << 27) // (15 << 18) == 34   # keccak-style k = 18
+    assert h2g.debug_commit_batch_chunk(11, 128) == 64
+    assert h2g.debug_commit_batch_chunk(16, 1 << 21) == 4     # 2^25 entries each: still batched
+    assert h2g.debug_commit_batch_chunk(16, (1 << 21) + 1) == 1
+    assert h2g.debug_commit_batch_chunk(20, 1 << 22) == 1     # C3 at k = 22: 13 x 2^22
+
+
+@pytest.mark.parametrize("k", range(8, 25))
+def test_commit_batch_chunk_is_a_batch_the_plan_takes(k):
+    """Whatever slab of 2^k points a rank commits on (the whole, down to an eighth: the SPMD
+    point slabs), against windows chosen for the slab's length or against the windows of the
+    whole SRS (Params::tables without h2g_params_set_slab), the batch commit_batch_chunk
+    chooses -- and every smaller one, the stage's remainder -- is a shape msm_plan accepts.
+    Before the rule asked the plan, 2^19-point slabs of k = 20 against c = 19 gave 18 sets
+    where 16 fit, and the slabs of k = 21 against c = 20 gave 9 and 14 where 8 fit."""
+    full_c = FIXED_C[k]
+    assert h2g.debug_msm_plan(1 << k, 0, fixed=True)["c"] == full_c
+    for parts in range(1, 9):
+        for r in range(parts):
+            n = ((r + 1) << k) // parts - (r << k) // parts   # shard_lo's slabs
+            slab_c = h2g.debug_msm_plan(n, 0, fixed=True)["c"]
+            for c in sorted({slab_c, full_c}):
+                chunk = h2g.debug_commit_batch_chunk(c, n)
+                assert 1 <= chunk <= 64
+                w = windows(c)
+                want = 1 if w * n > 1 << 25 else max(1, min(64, (1 << 27) // (w * n)))
+                fits = (1 << 22) >> (c - 1)   # sets of 2^(c-1) buckets within 2048 bins of 2^11 keys
+                assert chunk == max(1, min(want, fits)), (k, parts, c)
+                for nb in range(1, chunk + 1):
+                    assert variant(n=n, c=c, fixed=True, nbatch=nb) != REFUSED, (k, parts, c, nb)
+
+
+def test_commit_batch_chunk_is_bound_by_the_plan_only_on_short_slabs():
+    """the two never meet on one device (closest: k = 18, 34 sets of 2^16 against 64); the cases
+    worked by hand where they do"""
+    for k in range(8, 25):
+        c = FIXED_C[k]
+        w = windows(c)
+        if w << k <= 1 << 25:
+            assert min(64, (1 << 27) // (w << k)) <= (1 << 22) >> (c - 1), k
+    assert h2g.debug_commit_batch_chunk(19, 1 << 19) == 16                 # k = 20 on 2 ranks: was 18
+    assert h2g.debug_commit_batch_chunk(19, (1 << 20) // 3) == 16          # 3 ranks: was 27
+    assert h2g.debug_commit_batch_chunk(20, 1 << 20) == 8                  # k = 21 on 2 ranks: was 9
+    assert h2g.debug_commit_batch_chunk(20, (1 << 21) // 3) == 8           # 3 ranks: was 14

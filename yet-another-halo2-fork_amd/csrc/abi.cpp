@@ -179,15 +179,28 @@ int msm_fixed_host_impl(Device* d, const void* sc, const MsmFixedBase& fb, size_
   return msm_windows_to_host(d, 1, out, is_id, st);
 }
 
+// one more block of MSM_RING result slots and their events (the slots already handed out
+// stay where they are)
+static int msm_ring_grow(Device* d) {
+  void* blk = nullptr;
+  HIPCHK(hipHostMalloc(&blk, MSM_RING * sizeof(G1xyzz), hipHostMallocDefault));
+  d->h_ring.push_back(blk);
+  for (int i = 0; i < MSM_RING; i++) {
+    hipEvent_t e = nullptr;
+    HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    d->ring_ev.push_back(e);
+    d->ring_busy.push_back(0);
+  }
+  return H2G_OK;
+}
 // the asynchronous MSMs' streams, result ring and events (h2g_init creates them, right
 // after the device stream: see there)
 int msm_ring_init(Device* d) {
-  if (d->h_ring) return H2G_OK;
-  HIPCHK(hipHostMalloc(&d->h_ring, MSM_RING * sizeof(G1xyzz), hipHostMallocDefault));
+  if (!d->h_ring.empty()) return H2G_OK;
   // (the MSM streams at the device's greatest stream priority: measured, rejected)
-  for (int i = 0; i < MSM_STREAMS; i++) HIPCHK(hipStreamCreateWithFlags(&d->mstream[i], hipStreamNonBlocking));
-  for (int i = 0; i < MSM_RING; i++) HIPCHK(hipEventCreateWithFlags(&d->ring_ev[i], hipEventDisableTiming));
-  return H2G_OK;
+  for (int i = 0; i < MSM_STREAMS; i++)
+    if (!d->mstream[i]) HIPCHK(hipStreamCreateWithFlags(&d->mstream[i], hipStreamNonBlocking));
+  return msm_ring_grow(d);
 }
 
 // nb MSMs of n scalars each against the same fixed-base windows, launched as one batched
@@ -196,14 +209,22 @@ int msm_fixed_launch_batch(Device* d, const void* const* sc, int nb, const MsmFi
                            hipStream_t producer, MsmTicket* t) {
   if (nb < 1 || nb > MSM_MAX_BATCH) return fail(H2G_ERR_ARG, "msm: bad batch size");
   RCCHK(msm_ring_init(d));
+  // nb free result slots, searched from the one after the last taken; a stage that has more
+  // MSMs outstanding than the ring holds (all are launched before the first is collected)
+  // gets another block of slots
   int rings[MSM_MAX_BATCH];
   int got = 0;
-  for (int k = 0; k < MSM_RING && got < nb; k++) {
-    const int r = (d->next_ring + k) % MSM_RING;
-    if (!d->ring_busy[r]) rings[got++] = r;
+  for (;;) {
+    const int R = (int)d->ring_busy.size();
+    got = 0;
+    for (int k = 0; k < R && got < nb; k++) {
+      const int r = (d->next_ring + k) % R;
+      if (!d->ring_busy[r]) rings[got++] = r;
+    }
+    if (got == nb) break;
+    RCCHK(msm_ring_grow(d));
   }
-  if (got < nb) return fail(H2G_ERR_STATE, "msm: too many outstanding asynchronous MSMs");
-  d->next_ring = (rings[nb - 1] + 1) % MSM_RING;
+  d->next_ring = (rings[nb - 1] + 1) % (int)d->ring_busy.size();
   const int slot = d->next_slot;
   d->next_slot = (slot + 1) % MSM_STREAMS;
   hipStream_t ms = d->mstream[slot];
@@ -212,9 +233,8 @@ int msm_fixed_launch_batch(Device* d, const void* const* sc, int nb, const MsmFi
   HIPCHK(hipStreamWaitEvent(ms, d->ring_ev[rings[0]], 0));
   MsmPhaseEvents* pe = nullptr;
   if (n > 0) RCCHK(prof_begin(nb, &pe));
-  G1xyzz* host = reinterpret_cast<G1xyzz*>(d->h_ring);
   if (n == 0) {
-    for (int b = 0; b < nb; b++) std::memset(host + rings[b], 0, sizeof(G1xyzz));  // identity (ZZ = 0)
+    for (int b = 0; b < nb; b++) std::memset(d->ring_at(rings[b]), 0, sizeof(G1xyzz));  // identity (ZZ = 0)
   } else {
     MsmScalarList list;
     for (int b = 0; b < nb; b++) list.p[b] = reinterpret_cast<const Fr*>(sc[b]);
@@ -222,7 +242,7 @@ int msm_fixed_launch_batch(Device* d, const void* const* sc, int nb, const MsmFi
     else HIPCHK(msm_run_fixed_batch(list, nb, fb, off, n, &d->mws[slot], ms, pe));
     const G1xyzz* win = reinterpret_cast<const G1xyzz*>(d->mws[slot].windows.p);
     for (int b = 0; b < nb; b++)
-      HIPCHK(hipMemcpyAsync(host + rings[b], win + b, sizeof(G1xyzz), hipMemcpyDeviceToHost, ms));
+      HIPCHK(hipMemcpyAsync(d->ring_at(rings[b]), win + b, sizeof(G1xyzz), hipMemcpyDeviceToHost, ms));
   }
   for (int b = 0; b < nb; b++) {
     HIPCHK(hipEventRecord(d->ring_ev[rings[b]], ms));
@@ -243,7 +263,7 @@ int msm_fixed_launch(Device* d, const void* sc, const MsmFixedBase& fb, size_t o
 int msm_collect(Device* d, MsmTicket* t, uint64_t* out) {
   if (t->ring < 0) return fail(H2G_ERR_STATE, "msm: collect without launch");
   HIPCHK(hipEventSynchronize(t->done));
-  const G1xyzz* host = reinterpret_cast<const G1xyzz*>(d->h_ring) + t->ring;
+  const G1xyzz* host = d->ring_at(t->ring);
   const G1Affine r = msm_windows_host_finish(host, 1, t->c);
   std::memcpy(out, &r, 64);
   d->ring_busy[t->ring] = false;
@@ -255,14 +275,14 @@ int msm_collect(Device* d, MsmTicket* t, uint64_t* out) {
 int msm_collect_xyzz(Device* d, MsmTicket* t, G1xyzz* out) {
   if (t->ring < 0) return fail(H2G_ERR_STATE, "msm: collect without launch");
   HIPCHK(hipEventSynchronize(t->done));
-  *out = reinterpret_cast<const G1xyzz*>(d->h_ring)[t->ring];  // one window (fixed-base tickets)
+  *out = *d->ring_at(t->ring);  // one window (fixed-base tickets)
   d->ring_busy[t->ring] = false;
   t->ring = -1;
   return H2G_OK;
 }
 
 int msm_fence(Device* d, hipStream_t consumer) {
-  if (!d->h_ring) return H2G_OK;
+  if (d->h_ring.empty()) return H2G_OK;
   for (int i = 0; i < MSM_STREAMS; i++) {
     hipEvent_t e;
     HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -542,9 +562,9 @@ int h2g_shutdown(void) {
         (void)hipStreamDestroy(dev->mstream[i]);
       }
     for (int i = 0; i < MSM_STREAMS; i++) msm_free(&dev->mws[i]);
-    for (int i = 0; i < MSM_RING; i++)
-      if (dev->ring_ev[i]) (void)hipEventDestroy(dev->ring_ev[i]);
-    if (dev->h_ring) (void)hipHostFree(dev->h_ring);
+    for (hipEvent_t e : dev->ring_ev)
+      if (e) (void)hipEventDestroy(e);
+    for (void* blk : dev->h_ring) (void)hipHostFree(blk);
     dev->a.release();
     dev->b.release();
     dev->c.release();

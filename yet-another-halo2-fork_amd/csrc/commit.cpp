@@ -1,4 +1,5 @@
 // commit.cpp -- the commitment-MSM scheduler: launch, batch, slab-shard and collect.
+#include "multiopen.h"  // MsmRingGuard (the batches seam)
 #include "prover_state.h"
 
 using namespace h2g;
@@ -194,7 +195,14 @@ int commit_batch_chunk(const MsmFixedBase& tb, size_t n) {
   if (g_shard.world > 1) return 1;
   const uint64_t per = (uint64_t)tb.W * (n ? n : 1);
   if (per > H2G_MSM_BATCH_PER) return 1;
-  return (int)std::max<uint64_t>(1, std::min<uint64_t>(MSM_MAX_BATCH, max_entries / per));
+  int chunk = (int)std::max<uint64_t>(1, std::min<uint64_t>(MSM_MAX_BATCH, max_entries / per));
+  // ... and never more sets than the pipeline takes (msm_plan: sets x 2^(c-1) buckets within
+  // its partition).  Windows chosen for n never get there; a short slab against the windows
+  // of the whole SRS does (SPMD without h2g_params_set_slab: 2^19 points at c = 19 would
+  // batch 18 sets where 16 fit).
+  MsmPlan pl;
+  while (chunk > 1 && !msm_plan(n ? n : 1, tb.c, tb.W, 1, chunk, 0, &pl)) chunk--;
+  return chunk;
 }
 
 }  // namespace prv
@@ -281,3 +289,65 @@ int commit(Device* d, const Params& prm, const Fr* scalars, size_t n, int set, G
 }
 }  // namespace prv
 }  // namespace h2g
+
+// ---------------------------------------------------------------- test seams (include/h2g.h)
+// the per-launch capacities the prover's host loops split wide work by, in h2g.h's order
+int h2g_debug_limits(int32_t* out, int max, int* count) {
+  const int32_t v[] = {COPY_COLS_MAX, PREFIX_DIFF_MAX, COMPRESS_BATCH_MAX, LOOKUP_KEYS_BATCH_MAX, PERM_MAXC,
+                       LIN_MAXT,      NTT_MAX_BATCH,   POLY_INV_MAX_BATCH, MSM_MAX_BATCH,         MSM_RING};
+  constexpr int N = (int)(sizeof(v) / sizeof(v[0]));
+  static_assert(N == H2G_LIMIT_COUNT, "h2g.h lists the limits");
+  if (!count || max < 0 || (max > 0 && !out)) return fail(H2G_ERR_ARG, "debug_limits: bad argument");
+  for (int i = 0; i < N && i < max; i++) out[i] = v[i];
+  *count = N;
+  return H2G_OK;
+}
+
+// commit_batch_chunk for commitments of n points against windows of table_c bits
+int h2g_debug_commit_batch_chunk(int table_c, uint64_t n, int* chunk) {
+  if (!chunk) return fail(H2G_ERR_ARG, "debug_commit_batch_chunk: null argument");
+  if (table_c < 1 || table_c > 31) return fail(H2G_ERR_ARG, "debug_commit_batch_chunk: window bits out of range");
+  MsmFixedBase tb;
+  tb.c = table_c;
+  tb.W = msm_windows_for(table_c);
+  tb.n = (size_t)n;
+  *chunk = commit_batch_chunk(tb, (size_t)n);
+  return H2G_OK;
+}
+
+// nb_total MSMs in batches of `chunk`, every batch launched before the first result is
+// collected: commit_launch_batch's loop and commit_collect_all, against a base descriptor
+int h2g_debug_msm_batches_dev(uint64_t base, size_t base_offset, const void* const* d_scalars, int nb_total,
+                              int chunk, size_t n, uint64_t* out_affine, int32_t* is_identity) {
+  NEED_DEV_P();
+  Descriptor* ds = find_desc(base);
+  if (!ds || !ds->is_base) return fail(H2G_ERR_HANDLE, "unknown base descriptor");
+  if (!ds->fb.table) return fail(H2G_ERR_ARG, "debug_msm_batches: the descriptor has no fixed-base windows");
+  if (nb_total < 0 || (nb_total && (!d_scalars || !out_affine)))
+    return fail(H2G_ERR_ARG, "debug_msm_batches: null argument");
+  if (chunk < 1 || chunk > MSM_MAX_BATCH) return fail(H2G_ERR_ARG, "debug_msm_batches: chunk out of range");
+  if (base_offset > ds->n || n > ds->n - base_offset) return fail(H2G_ERR_ARG, "msm: bases.len() < size");
+  for (int b = 0; b < nb_total; b++)
+    if (n && !d_scalars[b]) return fail(H2G_ERR_ARG, "debug_msm_batches: null scalars");
+  // a batch the pipeline refuses is an argument error, found before anything is launched
+  MsmPlan pl;
+  for (int m : {std::min(chunk, nb_total), nb_total % chunk})
+    if (n && m > 0 && !msm_plan(n, ds->fb.c, ds->fb.W, 1, m, 0, &pl))
+      return fail(H2G_ERR_ARG, "debug_msm_batches: a shape the MSM refuses");
+  MsmRingGuard ring_guard{d};
+  std::vector<MsmTicket> tk((size_t)nb_total);
+  for (int b0 = 0; b0 < nb_total; b0 += chunk) {
+    const int m = std::min(chunk, nb_total - b0);
+    if (chunk < 2) RCCHK(msm_fixed_launch(d, d_scalars[b0], ds->fb, base_offset, n, d->stream, &tk[b0]));
+    else RCCHK(msm_fixed_launch_batch(d, d_scalars + b0, m, ds->fb, base_offset, n, d->stream, &tk[b0]));
+  }
+  std::vector<MsmTicket*> tp((size_t)nb_total);
+  for (int b = 0; b < nb_total; b++) tp[b] = &tk[b];
+  std::vector<G1Affine> cm((size_t)nb_total);
+  RCCHK(commit_collect_all(d, tp.data(), nb_total, cm.data()));
+  for (int b = 0; b < nb_total; b++) {
+    std::memcpy(out_affine + 8 * (size_t)b, &cm[b], 64);
+    if (is_identity) is_identity[b] = cm[b].is_identity() ? 1 : 0;
+  }
+  return H2G_OK;
+}

@@ -82,11 +82,11 @@ struct MsmRingGuard {
   Device* d;
   ~MsmRingGuard() {
     bool any = false;
-    for (bool b : d->ring_busy) any = any || b;
+    for (char b : d->ring_busy) any = any || b;
     if (!any) return;
     for (hipStream_t s : d->mstream)
       if (s) (void)hipStreamSynchronize(s);
-    for (bool& b : d->ring_busy) b = false;
+    for (char& b : d->ring_busy) b = 0;
   }
 };
 

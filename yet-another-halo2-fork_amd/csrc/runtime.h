@@ -145,7 +145,10 @@ struct Descriptor {
 // accumulation.  (Pipelining by stage instead -- partitions, accumulations and reductions
 // on three streams -- measured slower: a partition beside an accumulation gets CUs only
 // as the accumulation's blocks retire; profiles/r03/s3/ab_msm_pipe.)  Results land in a
-// pinned ring (one XYZZ point each).
+// pinned ring (one XYZZ point each): MSM_RING slots at first, and one more block of as many
+// whenever a launch finds too few free (a stage launches all its commitments before it
+// collects any, and may have any number of them).  Blocks are never moved or freed before
+// shutdown, so an outstanding ticket's slot stays where it is.
 static constexpr int MSM_STREAMS = 2;
 static constexpr int MSM_RING = 64;
 struct MsmTicket {
@@ -168,10 +171,11 @@ struct Device {
   MsmWorkspace mws[MSM_STREAMS];
   hipStream_t mstream[MSM_STREAMS] = {};
   int next_slot = 0;
-  void* h_ring = nullptr;  // pinned G1xyzz[MSM_RING]
-  hipEvent_t ring_ev[MSM_RING] = {};
-  bool ring_busy[MSM_RING] = {};
+  std::vector<void*> h_ring;        // pinned G1xyzz[MSM_RING] blocks: slot r is h_ring[r / MSM_RING][r % MSM_RING]
+  std::vector<hipEvent_t> ring_ev;  // one per slot
+  std::vector<char> ring_busy;
   int next_ring = 0;
+  G1xyzz* ring_at(int r) const { return reinterpret_cast<G1xyzz*>(h_ring[(size_t)r / MSM_RING]) + r % MSM_RING; }
   // the prover's column-transform stream (prove_impl: xs) and its NTT work buffer -- an NTT
   // on it must not share `work` with the prover's stream
   hipStream_t xstream = nullptr;

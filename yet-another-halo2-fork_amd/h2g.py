@@ -67,6 +67,10 @@ _SIGS = {
     "h2g_divide_by_vanishing_poly_dev": ([U64, VP, VP], I32),
     "h2g_debug_ntt_plan": ([U32, U64, U64, I32, I32, I32, I32, VP], I32),
     "h2g_debug_msm_plan": ([U64, I32, I32, I32, U32, VP], I32),
+    "h2g_debug_limits": ([ctypes.POINTER(ctypes.c_int32), I32, ctypes.POINTER(I32)], I32),
+    "h2g_debug_commit_batch_chunk": ([I32, U64, ctypes.POINTER(I32)], I32),
+    "h2g_debug_msm_batches_dev": ([U64, SZ, ctypes.POINTER(VP), I32, I32, SZ, U64P, ctypes.POINTER(ctypes.c_int32)],
+                                  I32),
     "h2g_fr_op": ([I32, U64P, U64P, U64P, U64P, SZ], I32),
     "h2g_fr_op_dev": ([I32, VP, VP, U64P, VP, SZ, VP], I32),
     "h2g_fr_batch_invert": ([U64P, SZ], I32),
@@ -504,6 +508,42 @@ def debug_msm_plan(n, c=0, fixed=False, nbatch=1, item_len=0):
     d["bytes"] = dict(zip(MSM_BUFFERS, pl.bytes))
     d["red"] = "plane" if pl.red_plane else "rscale"
     return d
+
+
+LIMITS = ("copy_cols", "prefix_diff", "compress_batch", "lookup_keys_batch", "perm_cols", "lin_terms", "ntt_batch",
+          "poly_inv_batch", "msm_batch", "msm_ring")  # H2G_LIMIT_*
+
+
+def debug_limits():
+    """h2g_debug_limits (test seam, host only): the per-launch capacities the prover's host loops
+    split wide work by -> {name: value} over LIMITS."""
+    n = I32(0)
+    check(lib().h2g_debug_limits(None, 0, ctypes.byref(n)))
+    assert n.value == len(LIMITS), "LIMITS mirrors H2G_LIMIT_*"
+    out = (ctypes.c_int32 * n.value)()
+    check(lib().h2g_debug_limits(out, n.value, ctypes.byref(n)))
+    return dict(zip(LIMITS, out))
+
+
+def debug_commit_batch_chunk(table_c, n):
+    """h2g_debug_commit_batch_chunk (test seam, host only): the commitments of n points that go
+    into one batched MSM against windows of table_c bits."""
+    ch = I32(0)
+    check(lib().h2g_debug_commit_batch_chunk(table_c, n, ctypes.byref(ch)))
+    return ch.value
+
+
+def debug_msm_batches_dev(base_handle, d_scalars, n, chunk, offset=0):
+    """h2g_debug_msm_batches_dev (test seam): MSMs of n scalars each (d_scalars: device pointers)
+    against a base descriptor from `offset`, launched in batches of `chunk` and collected after the
+    last launch -> (affine (len, 8), is_identity (len,))."""
+    nb = len(d_scalars)
+    ptrs = (VP * max(1, nb))(*d_scalars)
+    out = np.zeros((nb, 8), dtype=np.uint64)
+    ids = np.zeros(nb, dtype=np.int32)
+    check(lib().h2g_debug_msm_batches_dev(base_handle, offset, ptrs, nb, chunk, n, p64(out) if nb else None,
+                                          ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+    return out, ids
 
 
 # ----------------------------------------------------------------- poly ops
