@@ -410,109 +410,115 @@ H2G_HD G1xyzz29 xyzz29_madd(const G1xyzz29& p, const F29& qx, const F29& qy, boo
 // Carry-chained products.  The compiler reassociates a column's sum however the source
 // orders it: every column starts from 0 and the previous column's shifted carry is joined
 // with a separate 64-bit add (mul29's two-chain source and a single chain compile to the
-// same code).  H2G_PIN64 after every multiply-add (an empty asm on the accumulator) hides
-// each partial sum's origin from the reassociation, so the carry stays the column's first
-// addend: the join becomes the v_mad_u64_u32's own third operand.  Pinning less does not
-// hold: the unpinned rest of a column forms its own chain from 0 and is joined again.  The
-// product is then one dependent chain of mads; four waves per SIMD cover its latency.  The
-// pin is not free: the compiler puts one s_nop behind each (the wait state a reader of an
-// asm-defined register is owed), about half of what the joins were worth (DESIGN).
-// Same contracts as mul29 / sqr29 / mul29x2.
-#if defined(__HIP_DEVICE_COMPILE__)
-#define H2G_PIN64(x) asm("" : "+v"(x))
-#else
-#define H2G_PIN64(x) ((void)0)
-#endif
-#define H2G_MAC(acc, x, y)          \
-  do {                              \
-    acc += (uint64_t)(x) * (y);     \
-    H2G_PIN64(acc);                 \
-  } while (0)
+// same code).  Pinning each multiply-add with an empty asm keeps the carry as the column's
+// first addend but costs one wait state per pin (DESIGN).  So the device side of these forms
+// is the whole product as ONE asm statement (f29_asm.inc, generated by tools/f29_asm_gen.py,
+// whose header gives the column scheme and the register plan): a single chain of
+// multiply-adds with no joins, and one boundary pad per product.  The blocks compute the
+// same integers as mul29 / sqr29 / mul29x2, limb for limb (tests/test_f29_asm_cpu.py
+// interprets them), and the host side simply is those forms.  Same contracts.
+#include "f29_asm.inc"
+#define H2G_ASM_OUT9(p, r)                                                                                  \
+  [p##0] "=&v"((r).l[0]), [p##1] "=&v"((r).l[1]), [p##2] "=&v"((r).l[2]), [p##3] "=&v"((r).l[3]),          \
+      [p##4] "=&v"((r).l[4]), [p##5] "=&v"((r).l[5]), [p##6] "=&v"((r).l[6]), [p##7] "=&v"((r).l[7]),      \
+      [p##8] "=&v"((r).l[8])
+#define H2G_ASM_IO9(p, r)                                                                                   \
+  [p##0] "+v"((r).l[0]), [p##1] "+v"((r).l[1]), [p##2] "+v"((r).l[2]), [p##3] "+v"((r).l[3]),              \
+      [p##4] "+v"((r).l[4]), [p##5] "+v"((r).l[5]), [p##6] "+v"((r).l[6]), [p##7] "+v"((r).l[7]),          \
+      [p##8] "+v"((r).l[8])
+#define H2G_ASM_IN8(p, a)                                                                                   \
+  [p##0] "v"((a).l[0]), [p##1] "v"((a).l[1]), [p##2] "v"((a).l[2]), [p##3] "v"((a).l[3]),                  \
+      [p##4] "v"((a).l[4]), [p##5] "v"((a).l[5]), [p##6] "v"((a).l[6]), [p##7] "v"((a).l[7])
+#define H2G_ASM_IN9(p, a) H2G_ASM_IN8(p, a), [p##8] "v"((a).l[8])
+#define H2G_ASM_CONSTS(P)                                                                                   \
+  [M0] "s"(C29<P>::M[0]), [M1] "s"(C29<P>::M[1]), [M2] "s"(C29<P>::M[2]), [M3] "s"(C29<P>::M[3]),          \
+      [M4] "s"(C29<P>::M[4]), [M5] "s"(C29<P>::M[5]), [M6] "s"(C29<P>::M[6]), [M7] "s"(C29<P>::M[7]),      \
+      [M8] "s"(C29<P>::M[8]), [INV] "s"(C29<P>::INV), [MASK] "s"(F29_MASK)
 template <class P>
 H2G_HD F29 mul29_acc(const F29& a, const F29& b) {
-  uint32_t m[9];
+#if defined(__HIP_DEVICE_COMPILE__)
   F29 r;
-  uint64_t acc = 0;
-#pragma unroll
-  for (int k = 0; k < 17; k++) {
-    const int i0 = k > 8 ? k - 8 : 0, i1 = k > 8 ? 8 : k;
-    H2G_MAC(acc, a.l[i0], b.l[k - i0]);
-#pragma unroll
-    for (int i = i0 + 1; i <= i1; i++) H2G_MAC(acc, a.l[i], b.l[k - i]);
-    if (k < 9) {
-#pragma unroll
-      for (int i = 0; i < k; i++) H2G_MAC(acc, m[i], C29<P>::M[k - i]);
-      m[k] = ((uint32_t)acc * C29<P>::INV) & F29_MASK;
-      H2G_MAC(acc, m[k], C29<P>::M[0]);
-    } else {
-#pragma unroll
-      for (int i = k - 8; i < 9; i++) H2G_MAC(acc, m[i], C29<P>::M[k - i]);
-      r.l[k - 9] = (uint32_t)acc & F29_MASK;
-    }
-    acc >>= 29;
-  }
-  r.l[8] = (uint32_t)acc;
+  asm(H2G_ASM_MUL29
+      : H2G_ASM_OUT9(r, r)
+      : H2G_ASM_IN9(a, a), H2G_ASM_IN9(b, b), H2G_ASM_CONSTS(P)
+      : "vcc", H2G_ASM_ACC_CLOBBER);
   return r;
+#else
+  return mul29<P>(a, b);
+#endif
 }
 template <class P>
 H2G_HD F29 sqr29_acc(const F29& a) {
-  uint32_t m[9], d[9];
+#if defined(__HIP_DEVICE_COMPILE__)
+  F29 r, d;
 #pragma unroll
-  for (int i = 0; i < 9; i++) d[i] = a.l[i] << 1;
-  F29 r;
-  uint64_t acc = 0;
-#pragma unroll
-  for (int k = 0; k < 17; k++) {
-    const int i0 = k > 8 ? k - 8 : 0;
-    if (2 * i0 < k) H2G_MAC(acc, d[i0], a.l[k - i0]);
-    else H2G_MAC(acc, a.l[k / 2], a.l[k / 2]);  // k = 0, 16: the square is the only term
-#pragma unroll
-    for (int i = i0 + 1; 2 * i < k; i++) H2G_MAC(acc, d[i], a.l[k - i]);
-    if ((k & 1) == 0 && 2 * i0 < k) H2G_MAC(acc, a.l[k / 2], a.l[k / 2]);
-    if (k < 9) {
-#pragma unroll
-      for (int i = 0; i < k; i++) H2G_MAC(acc, m[i], C29<P>::M[k - i]);
-      m[k] = ((uint32_t)acc * C29<P>::INV) & F29_MASK;
-      H2G_MAC(acc, m[k], C29<P>::M[0]);
-    } else {
-#pragma unroll
-      for (int i = k - 8; i < 9; i++) H2G_MAC(acc, m[i], C29<P>::M[k - i]);
-      r.l[k - 9] = (uint32_t)acc & F29_MASK;
-    }
-    acc >>= 29;
-  }
-  r.l[8] = (uint32_t)acc;
+  for (int i = 0; i < 8; i++) d.l[i] = a.l[i] << 1;
+  asm(H2G_ASM_SQR29
+      : H2G_ASM_OUT9(r, r)
+      : H2G_ASM_IN9(a, a), H2G_ASM_IN8(d, d), H2G_ASM_CONSTS(P)
+      : "vcc", H2G_ASM_ACC_CLOBBER);
   return r;
+#else
+  return sqr29<P>(a);
+#endif
 }
 template <class P>
 H2G_HD F29 mul29x2_acc(const F29& a, const F29& b, const F29& c, const F29& d) {
-  uint32_t m[9];
+#if defined(__HIP_DEVICE_COMPILE__)
   F29 r;
-  uint64_t acc = 0;
-#pragma unroll
-  for (int k = 0; k < 17; k++) {
-    const int i0 = k > 8 ? k - 8 : 0, i1 = k > 8 ? 8 : k;
-    H2G_MAC(acc, a.l[i0], b.l[k - i0]);
-    H2G_MAC(acc, c.l[i0], d.l[k - i0]);
-#pragma unroll
-    for (int i = i0 + 1; i <= i1; i++) {
-      H2G_MAC(acc, a.l[i], b.l[k - i]);
-      H2G_MAC(acc, c.l[i], d.l[k - i]);
-    }
-    if (k < 9) {
-#pragma unroll
-      for (int i = 0; i < k; i++) H2G_MAC(acc, m[i], C29<P>::M[k - i]);
-      m[k] = ((uint32_t)acc * C29<P>::INV) & F29_MASK;
-      H2G_MAC(acc, m[k], C29<P>::M[0]);
-    } else {
-#pragma unroll
-      for (int i = k - 8; i < 9; i++) H2G_MAC(acc, m[i], C29<P>::M[k - i]);
-      r.l[k - 9] = (uint32_t)acc & F29_MASK;
-    }
-    acc >>= 29;
-  }
-  r.l[8] = (uint32_t)acc;
+  asm(H2G_ASM_MUL29X2
+      : H2G_ASM_OUT9(r, r)
+      : H2G_ASM_IN9(a, a), H2G_ASM_IN9(b, b), H2G_ASM_IN9(c, c), H2G_ASM_IN9(d, d), H2G_ASM_CONSTS(P)
+      : "vcc", H2G_ASM_ACC_CLOBBER);
   return r;
+#else
+  return mul29x2<P>(a, b, c, d);
+#endif
+}
+// a = REDC(a b) and c = REDC(a b + c d) in the registers of a / of c: where the old value
+// dies in the product (a loop-carried coordinate) the result needs no copy
+template <class P>
+H2G_HD void mul29_acc_to(F29& a, const F29& b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  F29 m;
+  asm(H2G_ASM_MUL29_IP
+      : H2G_ASM_IO9(a, a), H2G_ASM_OUT9(m, m)
+      : H2G_ASM_IN9(b, b), H2G_ASM_CONSTS(P)
+      : "vcc", H2G_ASM_ACC_CLOBBER);
+#else
+  a = mul29<P>(a, b);
+#endif
+}
+template <class P>
+H2G_HD void mul29x2_acc_to(F29& c, const F29& a, const F29& b, const F29& d) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  F29 m;
+  asm(H2G_ASM_MUL29X2_IP
+      : H2G_ASM_IO9(c, c), H2G_ASM_OUT9(m, m)
+      : H2G_ASM_IN9(a, a), H2G_ASM_IN9(b, b), H2G_ASM_IN9(d, d), H2G_ASM_CONSTS(P)
+      : "vcc", H2G_ASM_ACC_CLOBBER);
+#else
+  c = mul29x2<P>(a, b, c, d);
+#endif
+}
+// two independent products, r0 = REDC(a0 b0) and r1 = REDC(a1 b1), their chains alternating
+// instruction by instruction: at 2-3 waves per SIMD (the NTT passes) a lone chain's
+// latency is not covered
+template <class P>
+H2G_HD void mul29_pair(F29& r0, F29& r1, const F29& a0, const F29& b0, const F29& a1, const F29& b1) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  F29 t0, t1;
+  asm(H2G_ASM_MUL29_PAIR
+      : H2G_ASM_OUT9(r, t0), H2G_ASM_OUT9(xr, t1)
+      : H2G_ASM_IN9(a, a0), H2G_ASM_IN9(b, b0), H2G_ASM_IN9(xa, a1), H2G_ASM_IN9(xb, b1), H2G_ASM_CONSTS(P)
+      : "vcc", H2G_ASM_ACC_CLOBBER, H2G_ASM_ACC2_CLOBBER);
+  r0 = t0;
+  r1 = t1;
+#else
+  const F29 t0 = mul29<P>(a0, b0), t1 = mul29<P>(a1, b1);
+  r0 = t0;
+  r1 = t1;
+#endif
 }
 
 // a - b + K M, normalised, in one pass: a signed carry chain (subtract, add the constant's
@@ -561,11 +567,11 @@ H2G_HD int xyzz29_madd_acc(G1xyzz29& p, const F29& qx, const F29& qy) {
   const F29 PP = sqr29_acc<P>(Pp);
   const F29 Q = mul29_acc<P>(p.X, PP);
   const F29 PPP = mul29_acc<P>(Pp, PP);
-  p.ZZ = mul29_acc<P>(p.ZZ, PP);
-  p.ZZZ = mul29_acc<P>(p.ZZZ, PPP);
+  mul29_acc_to<P>(p.ZZ, PP);
+  mul29_acc_to<P>(p.ZZZ, PPP);
   const F29 R2 = sqr29_acc<P>(R);
   p.X = subn29<P, 32>(R2, add29(add29(PPP, Q), Q));  // R^2 - PPP - 2Q
-  p.Y = mul29x2_acc<P>(R, sub29<P, 64, 29>(Q, p.X), p.Y, sub29<P, 16, 29>(F29{}, PPP));  // R (Q - X3) - Y PPP
+  mul29x2_acc_to<P>(p.Y, R, sub29<P, 64, 29>(Q, p.X), sub29<P, 16, 29>(F29{}, PPP));  // R (Q - X3) - Y PPP
   return st;
 }
 

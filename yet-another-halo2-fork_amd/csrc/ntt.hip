@@ -15,9 +15,9 @@
 // One wavefront owns CPW = 64 / 2^(m-3) adjacent columns; every lane holds 8
 // elements of one column in registers.  A 2^m-point DIF = one in-register
 // radix-8 round on the top 3 index bits, (m-3) lane<->register bit swaps by
-// __shfl_xor (no LDS staging, no barriers), and a second in-register round on
-// the low m-3 bits.  Global accesses are runs of >= 8 x 32 B across the lanes
-// of one instruction.  Inter-pass twiddles are streamed from per-pass tables
+// v_permlane32_swap / v_permlane16_swap / a DPP row rotation (no LDS, no barriers), and a
+// second in-register round on the low m-3 bits.  Global accesses are runs of >= 8 x 32 B
+// across the lanes of one instruction.  Inter-pass twiddles are streamed from per-pass tables
 // (NttTables::pass_tw), built once from a 2-level table w^E = lo[E mod 2^b] * hi[E >> b].
 #include <algorithm>
 #include <type_traits>
@@ -76,12 +76,6 @@ __device__ __forceinline__ uint32_t brev_bits(uint32_t x, int m) { return __brev
 
 __device__ __forceinline__ F29 ld29(const Fr* p) { return raw29(ld_fr(p)); }
 __device__ __forceinline__ void st29(Fr* p, const F29& v) { st_fr(p, pack29<FrParams>(v)); }
-__device__ __forceinline__ F29 shfl_xor29(const F29& v, int mask) {
-  F29 r;
-#pragma unroll
-  for (int i = 0; i < 9; i++) r.l[i] = (uint32_t)__shfl_xor((int)v.l[i], mask);
-  return r;
-}
 __device__ __forceinline__ F29 sel29(int c, const F29& a, const F29& b) {
   F29 r;
 #pragma unroll
@@ -99,6 +93,9 @@ __device__ __forceinline__ void sfor(F&& f) {
   }
 }
 
+// The passes' products are the single-chain block forms of f29.h: two independent products
+// as one pair block (mul29_pair, their chains alternate), a lone one as the single block.
+
 // a - b + K_s M for stage s: K_s = 2^(s+2)
 template <int S>
 __device__ __forceinline__ F29 nsub29(const F29& a, const F29& b) {
@@ -115,30 +112,61 @@ template <int M>
 struct WaveDif29 {
   static constexpr int LPC = 1 << (M - 3);  // lanes per column
   static constexpr int CPW = 64 / LPC;      // columns per wave
+  // register index of butterfly p < 4 of a stage on register bit T (its partner: + 2^T)
+  static constexpr int qof(int p, int T) { return ((p >> T) << (T + 1)) | (p & ((1 << T) - 1)); }
   template <int T>  // round A, row bit M-3+T (stage 2 - T)
   __device__ static __forceinline__ void stage_a(F29 x[8], const F29* w, int rg) {
     constexpr int htlog = (M - 3) + T;
+    F29 d[4];
 #pragma unroll
     for (int p = 0; p < 4; p++) {
-      const int q = ((p >> T) << (T + 1)) | (p & ((1 << T) - 1));
-      const int j = rg + (p & ((1 << T) - 1)) * LPC;
+      const int q = qof(p, T);
       const F29 a = x[q], b = x[q + (1 << T)];
       x[q] = norm29(add29(a, b));
-      x[q + (1 << T)] = mul29<FrParams>(nsub29<2 - T>(a, b), w[j << (M - 1 - htlog)]);
+      d[p] = nsub29<2 - T>(a, b);
     }
+    // the four products are independent: two pair blocks
+    sfor<0, 2>([&](auto hc) {
+      constexpr int p0 = 2 * decltype(hc)::value, p1 = p0 + 1;
+      const int j0 = rg + (p0 & ((1 << T) - 1)) * LPC, j1 = rg + (p1 & ((1 << T) - 1)) * LPC;
+      mul29_pair<FrParams>(x[qof(p0, T) + (1 << T)], x[qof(p1, T) + (1 << T)], d[p0], w[j0 << (M - 1 - htlog)], d[p1],
+                   w[j1 << (M - 1 - htlog)]);
+    });
     if constexpr (T > 0) stage_a<T - 1>(x, w, rg);
   }
-  template <int B>  // register bit B <-> lane bit
+  // register bit B <-> lane bit: the lower lane's high register changes places with the
+  // upper lane's low register.  Lane distances 32 and 16 are exactly v_permlane32_swap /
+  // v_permlane16_swap (vdst = the low register: its upper lanes or odd rows swap with the
+  // lower lanes or even rows of src); distance 8 (M = 6 only) is a select, a DPP rotation
+  // of the row by 8 and a select.  No LDS traffic.
+  template <int B>
   __device__ static __forceinline__ void swap_bits(F29 x[8], int rg) {
     if constexpr (B < M - 3) {
+      constexpr int dist = CPW << B;
       const int lb = (rg >> B) & 1;
 #pragma unroll
       for (int p = 0; p < 4; p++) {
-        const int q = ((p >> B) << (B + 1)) | (p & ((1 << B) - 1));
-        const F29 lo_v = x[q], hi_v = x[q | (1 << B)];
-        const F29 recv = shfl_xor29(sel29(lb, lo_v, hi_v), CPW << B);
-        x[q] = sel29(lb, recv, lo_v);
-        x[q | (1 << B)] = sel29(lb, hi_v, recv);
+        const int q = qof(p, B);
+        if constexpr (dist >= 16) {
+#pragma unroll
+          for (int i = 0; i < 9; i++) {
+            const auto r = dist == 32 ? __builtin_amdgcn_permlane32_swap(x[q].l[i], x[q | (1 << B)].l[i], false, false)
+                                      : __builtin_amdgcn_permlane16_swap(x[q].l[i], x[q | (1 << B)].l[i], false, false);
+            x[q].l[i] = r[0];
+            x[q | (1 << B)].l[i] = r[1];
+          }
+        } else {
+          static_assert(dist == 8, "lane distance of a register/lane bit swap");
+          const F29 lo_v = x[q], hi_v = x[q | (1 << B)];
+          const F29 send = sel29(lb, lo_v, hi_v);
+          F29 recv;
+#pragma unroll
+          for (int i = 0; i < 9; i++)
+            recv.l[i] =
+                (uint32_t)__builtin_amdgcn_update_dpp(0, (int)send.l[i], 0x128 /* row_ror:8 */, 0xf, 0xf, false);
+          x[q] = sel29(lb, recv, lo_v);
+          x[q | (1 << B)] = sel29(lb, hi_v, recv);
+        }
       }
       swap_bits<B + 1>(x, rg);
     }
@@ -147,20 +175,46 @@ struct WaveDif29 {
   __device__ static __forceinline__ void stage_b(F29 x[8], const F29* w) {
     if constexpr (T >= 0) {
       constexpr int S = 3 + (M - 4 - T);
+      F29 d[4];
 #pragma unroll
       for (int p = 0; p < 4; p++) {
-        const int q = ((p >> T) << (T + 1)) | (p & ((1 << T) - 1));
-        const int j = q & ((1 << T) - 1);
+        const int q = qof(p, T);
         const F29 a = x[q], b = x[q + (1 << T)];
         x[q] = norm29(add29(a, b));
-        x[q + (1 << T)] = j == 0 ? norm29(nsub29<S>(a, b)) : mul29<FrParams>(nsub29<S>(a, b), w[j << (M - 1 - T)]);
+        d[p] = nsub29<S>(a, b);
+      }
+      // butterfly p takes twiddle j = p mod 2^T, none for j = 0: T = 0 has no product,
+      // T = 1 has p = 1, 3 (a pair), T = 2 has p = 1, 2 (a pair) and p = 3
+      constexpr int hi = 1 << T;
+      x[qof(0, T) + hi] = norm29(d[0]);
+      if constexpr (T == 0) {
+        x[qof(1, T) + hi] = norm29(d[1]);
+        x[qof(2, T) + hi] = norm29(d[2]);
+        x[qof(3, T) + hi] = norm29(d[3]);
+      } else if constexpr (T == 1) {
+        x[qof(2, T) + hi] = norm29(d[2]);
+        const F29 w1 = w[1 << (M - 1 - T)];
+        mul29_pair<FrParams>(x[qof(1, T) + hi], x[qof(3, T) + hi], d[1], w1, d[3], w1);
+      } else {
+        static_assert(T == 2, "round B has at most three stages");
+        mul29_pair<FrParams>(x[qof(1, T) + hi], x[qof(2, T) + hi], d[1], w[1 << (M - 1 - T)], d[2],
+                             w[2 << (M - 1 - T)]);
+        x[qof(3, T) + hi] = mul29_acc<FrParams>(d[3], w[3 << (M - 1 - T)]);
       }
       stage_b<T - 1>(x, w);
     }
   }
   __device__ static __forceinline__ void run(F29 x[8], const F29* w, int rg) {
     stage_a<2>(x, w, rg);
-    swap_bits<0>(x, rg);
+    if constexpr (M > 3) {
+      // A lane swap must not read a register within two wait states of its write, and the
+      // compiler counts them only for its own instructions.  A product block's last write is
+      // its top limb (the closing move), so the top limbs of round A's last products pass
+      // through two states here, once; every other limb is written earlier in its block
+      // (tests/test_ntt_inst_count_cpu.py checks the emitted code for it).
+      asm("s_nop 1" : "+v"(x[1].l[8]), "+v"(x[3].l[8]), "+v"(x[5].l[8]), "+v"(x[7].l[8]));
+      swap_bits<0>(x, rg);
+    }
     stage_b<M - 4>(x, w);
   }
 
@@ -265,11 +319,14 @@ ntt_pass29_kernel(Fr* data, NttIo io, int first, uint64_t n_in, NttTables tab, c
   }
   D::run(x, w, rg);
   const uint64_t ilow = g * D::CPW + c;
-  sfor<0, 8>([&](auto qc) {
-    constexpr int qq = decltype(qc)::value;
-    const uint32_t k = brev_bits(D::rpos(qq, rg), M);
-    const F29 tw = ld29(ptw + (uint64_t)k * S + ilow);
-    st29(data + base + c + (uint64_t)k * S, mul29<FrParams>(x[qq], tw));
+  sfor<0, 4>([&](auto qc) {
+    constexpr int q0 = 2 * decltype(qc)::value, q1 = q0 + 1;
+    const uint32_t k0 = brev_bits(D::rpos(q0, rg), M), k1 = brev_bits(D::rpos(q1, rg), M);
+    F29 y0, y1;
+    mul29_pair<FrParams>(y0, y1, x[q0], ld29(ptw + (uint64_t)k0 * S + ilow), x[q1],
+                         ld29(ptw + (uint64_t)k1 * S + ilow));
+    st29(data + base + c + (uint64_t)k0 * S, y0);
+    st29(data + base + c + (uint64_t)k1 * S, y1);
   });
 }
 
@@ -317,10 +374,14 @@ ntt_pass29p_kernel(Fr* data, NttTables tab, const Fr* __restrict__ ptw, int L, i
     D::run(x, w, rg);
     __builtin_amdgcn_sched_barrier(0);
     const uint64_t ilow = (cur % groups) * D::CPW + c;
-    sfor<0, 8>([&](auto qc) {
-      constexpr int qq = decltype(qc)::value;
-      const uint32_t k = brev_bits(D::rpos(qq, rg), M);
-      st29(data + base + c + (uint64_t)k * S, mul29<FrParams>(x[qq], ld29(ptw + (uint64_t)k * S + ilow)));
+    sfor<0, 4>([&](auto qc) {
+      constexpr int q0 = 2 * decltype(qc)::value, q1 = q0 + 1;
+      const uint32_t k0 = brev_bits(D::rpos(q0, rg), M), k1 = brev_bits(D::rpos(q1, rg), M);
+      F29 y0, y1;
+      mul29_pair<FrParams>(y0, y1, x[q0], ld29(ptw + (uint64_t)k0 * S + ilow), x[q1],
+                         ld29(ptw + (uint64_t)k1 * S + ilow));
+      st29(data + base + c + (uint64_t)k0 * S, y0);
+      st29(data + base + c + (uint64_t)k1 * S, y1);
     });
     if (!more) break;
   }
@@ -431,22 +492,35 @@ ntt_last29_kernel(const Fr* data, NttIo io, uint64_t out_len, NttTables tab, int
   });
   D::run(x, w, rg);
   const uint64_t kstride = 1ull << (L - M);
-  sfor<0, 8>([&](auto qc) {
-    constexpr int qq = decltype(qc)::value;
-    const uint32_t k = brev_bits(D::rpos(qq, rg), M);
-    const uint64_t y = k0 + mid_nat + (uint64_t)k * kstride;
-    if (!TRUNC || y < out_len) {
-      if constexpr (ONE) {
-        st29(out + y, sub_m_if_ge29<FrParams>(reduce29<FrParams>(x[qq])));
-      } else {
-        const uint32_t md = mod3(y);
-        // the epilogue constant (scale and / or zeta power) also brings the value below
-        // 2.6 M; two conditional subtractions reach [0, M)
-        const F29 v = mul29<FrParams>(x[qq], sel29(md == 1, k29.mul[1], sel29(md == 2, k29.mul[2], k29.mul[0])));
-        st29(out + y, sub_m_if_ge29<FrParams>(sub_m_if_ge29<FrParams>(v)));
+  auto yof = [&](int qq) { return k0 + mid_nat + (uint64_t)brev_bits(D::rpos(qq, rg), M) * kstride; };
+  if constexpr (ONE) {
+    sfor<0, 8>([&](auto qc) {
+      constexpr int qq = decltype(qc)::value;
+      const uint64_t y = yof(qq);
+      if (!TRUNC || y < out_len) st29(out + y, sub_m_if_ge29<FrParams>(reduce29<FrParams>(x[qq])));
+    });
+  } else {
+    // the epilogue constant (scale and / or zeta power) also brings the value below 2.6 M;
+    // two conditional subtractions reach [0, M).  The products go in pairs; where only one
+    // element of a pair is stored, the other's product is discarded.
+    auto kof = [&](uint64_t y) {
+      const uint32_t md = mod3(y);
+      return sel29(md == 1, k29.mul[1], sel29(md == 2, k29.mul[2], k29.mul[0]));
+    };
+    sfor<0, 4>([&](auto qc) {
+      // registers q and q + 4 hold outputs N / 8 apart (q's bits are y's top three), so a pair
+      // lies on one side of a truncation at a multiple of N / 4 and at most an eighth of the
+      // outputs sits in pairs that straddle another one
+      constexpr int q0 = decltype(qc)::value, q1 = q0 + 4;
+      const uint64_t y0 = yof(q0), y1 = yof(q1);
+      if (!TRUNC || y0 < out_len || y1 < out_len) {  // a pair wholly behind the truncation: no product
+        F29 v0, v1;
+        mul29_pair<FrParams>(v0, v1, x[q0], kof(y0), x[q1], kof(y1));
+        if (!TRUNC || y0 < out_len) st29(out + y0, sub_m_if_ge29<FrParams>(sub_m_if_ge29<FrParams>(v0)));
+        if (!TRUNC || y1 < out_len) st29(out + y1, sub_m_if_ge29<FrParams>(sub_m_if_ge29<FrParams>(v1)));
       }
-    }
-  });
+    });
+  }
 }
 
 // ---------------------------------------------------------------------------
