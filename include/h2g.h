@@ -33,7 +33,8 @@ enum {
   H2G_ERR_DEVICE = 2,  /* HIP runtime error */
   H2G_ERR_NOMEM = 3,
   H2G_ERR_STATE = 4,   /* not initialised */
-  H2G_ERR_HANDLE = 5   /* unknown descriptor / domain handle */
+  H2G_ERR_HANDLE = 5,  /* unknown descriptor / domain handle */
+  H2G_ERR_UNSATISFIED = 6 /* create_proof's self-check: the witness does not satisfy the circuit */
 };
 
 int h2g_abi_version(void);
@@ -636,6 +637,78 @@ typedef struct {
   uint32_t num_copies;
 } h2g_check_inputs;
 int h2g_check_witness(uint64_t pk, const h2g_check_inputs* in, h2g_check_failure* out, size_t cap, uint64_t* total);
+
+/* ---- the prover's self-checks: refuse a proof that will not verify, and say why -----------
+ * h2g_create_proof* accepts any advice; by default (H2G_SELFCHECK_OFF) a witness that breaks a
+ * gate, a copy or a shuffle gives H2G_OK and bytes the verifier rejects.  Per key, like
+ * h2g_pk_set_multiopen (an unknown mode: H2G_ERR_ARG):
+ *   H2G_SELFCHECK_VERDICT    after its evaluations the prover forms the verifier's expected_h
+ *       from the very scalars, challenges and instances of the proof (the code h2g_verify_proof
+ *       runs) and compares it with h(x), the one condition of verify_proof that depends on the
+ *       witness.  Equal: the proof is returned, byte for byte mode 0's.  Different: the call
+ *       returns H2G_ERR_UNSATISFIED, writes no proof (*proof_len = 0) and leaves the key
+ *       usable; h2g_last_self_check then says where, located on the run's own data:
+ *         kinds 1 / 2  gates, as h2g_check_witness defines them, on the advice with the blinding
+ *                      rows this proof drew and its own challenges
+ *         kind 6       circuit's permutation product does not close: z_last[u] != 1, index =
+ *                      the last column set, row = u.  Some copy constraint is broken; the copy
+ *                      list is not part of the key, so h2g_check_witness with the list names it
+ *         kind 4       shuffle `index`: its product does not close (row = H2G_CHECK_NO_ROW)
+ *         kind 10      the identity fails and none of the above says where
+ *       A wrong witness passes with probability about d / r (d the circuit's degree times n, r
+ *       the 254-bit field order): x is drawn after the commitments.
+ *   H2G_SELFCHECK_ARGUMENTS  the above, and the reference's `sanity-checks` assertions while
+ *       each argument is built (device kernels behind the kernel that made the argument; no RNG
+ *       draw, nothing written to the transcript: a valid witness gives mode 0's bytes):
+ *         kind 9  the advice as handed in is nonzero at row >= u of unblinded column `index`
+ *                 (prover.rs:418-421; a blinded column's rows there are overwritten and are
+ *                 not asked)                                         -> H2G_ERR_UNSATISFIED
+ *         kind 8  lookup `index`: permuted pair, A'[row] is neither S'[row] nor A'[row - 1]
+ *                 (lookup/prover.rs:475-488)                         -> H2G_ERR_STATE
+ *         kind 6  column set `index`'s permutation product (ours; the reference asserts nothing
+ *                 here): at row < u the recurrence against sigma and delta^c omega^row fails, or
+ *                 at row 0 the set does not start at the previous set's z[u] (set 0: at one)
+ *                                                                    -> H2G_ERR_STATE
+ *         kind 7  product `index` (a lookup's, or num_lookups + a shuffle's): z[0] != 1 or the
+ *                 recurrence from row to row + 1 fails (lookup/prover.rs:269-305,
+ *                 shuffle/prover.rs:176-191)                         -> H2G_ERR_STATE
+ *                 row = u: a lookup's z[u] != 1                      -> H2G_ERR_UNSATISFIED
+ *       H2G_ERR_STATE: no witness can cause it; the message names the library.
+ * A lookup input missing from its table stays H2G_ERR_ARG in every mode.  With a shard or SPMD
+ * transport installed and mode != 0, create_proof* returns H2G_ERR_STATE before any work.
+ * h2g_last_self_check: the records of the last h2g_create_proof* in this process (library state
+ * under the library's lock, as h2g_last_challenges is: callers that prove from several threads
+ * read it before the next proof starts; none after a proof that was
+ * returned or failed for another reason), sorted by (circuit, kind, index, row); `reserved`
+ * carries the circuit's index in the proof (0 from h2g_check_witness).  *total is exact; the
+ * library keeps at most 4096 records per circuit. */
+enum { H2G_SELFCHECK_OFF = 0, H2G_SELFCHECK_VERDICT = 1, H2G_SELFCHECK_ARGUMENTS = 2 };
+enum {
+  H2G_CHECK_PERMUTATION = 6,  /* set `index`'s grand product: closing value (row = u), recurrence (row < u) */
+  H2G_CHECK_PRODUCT = 7,      /* lookup / shuffle product `index` at `row` */
+  H2G_CHECK_PERMUTED_PAIR = 8,/* lookup `index`: the permuted pair at `row` */
+  H2G_CHECK_UNUSABLE_ROW = 9, /* unblinded advice column `index` is nonzero at unusable row `row` */
+  H2G_CHECK_IDENTITY = 10     /* the vanishing identity fails at x; nothing located */
+};
+int h2g_pk_set_self_check(uint64_t pk, int mode);
+int h2g_last_self_check(h2g_check_failure* out, size_t cap, uint64_t* total);
+/* test seams (tests/test_selfcheck_kernels_gpu.py): the product and permuted-pair kernels on device
+ * arrays of any n >= 2 (z: n elements, the others u; 1 <= u < n), max_blocks > 0 caps the grid.
+ * d_num_b == d_den_b == NULL: the one-factor (shuffle) form, z[i+1] (gamma + den_a[i]) = z[i]
+ * (gamma + num_a[i]).  Records {kind, 0, row, 0} sorted by row, min(cap, failures) of them. */
+int h2g_debug_selfcheck_product_dev(const void* d_z, const void* d_num_a, const void* d_num_b, const void* d_den_a,
+                                    const void* d_den_b, const uint64_t beta[4], const uint64_t gamma[4], uint64_t n,
+                                    uint64_t u, int max_blocks, h2g_check_failure* out, size_t cap, uint64_t* total);
+int h2g_debug_selfcheck_permuted_dev(const void* d_a, const void* d_s, uint64_t u, int max_blocks,
+                                     h2g_check_failure* out, size_t cap, uint64_t* total);
+/* ... and the permutation-product kernel on one column set of m columns (1 <= m <= 64; more than 8
+ * go in several launches, as in the prover): d_values / d_sigmas are host arrays of m device
+ * pointers (u elements each), d_z has u + 1, delta_pows is m x 4 (delta^c of each column),
+ * first the value z[0] must have (NULL: one).  Records {6, 0, row, 0}. */
+int h2g_debug_selfcheck_permutation_dev(const void* d_z, const uint64_t* first, const void* const* d_values,
+                                        const void* const* d_sigmas, const uint64_t* delta_pows, int m,
+                                        const uint64_t beta[4], const uint64_t gamma[4], const uint64_t omega[4],
+                                        uint64_t u, h2g_check_failure* out, size_t cap, uint64_t* total);
 
 /* ---- verify_proof (halo2_backend/src/plonk/verifier.rs:58-512) with the KZG multi-open
  * verifiers (poly/kzg/multiopen/{shplonk,gwc}/verifier.rs) and DualMSM::check

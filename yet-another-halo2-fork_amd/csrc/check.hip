@@ -18,6 +18,7 @@
 // wrong everywhere does not serialise on the counter.  Records are written with ordinary
 // 16-byte vector stores.
 #include "check.h"
+#include "check_sink.h"
 #include "fr_io.h"
 #include "gate_prog.h"
 
@@ -29,40 +30,6 @@ static unsigned check_grid(size_t n) {
   size_t g = (n + CK_T - 1) / CK_T;
   const size_t cap = 256 * 16;
   return (unsigned)(g < cap ? (g ? g : 1) : cap);
-}
-
-// a wave's view of the sink: wave-uniform (every lane active at a push sees the same values;
-// a wave's lowest lane takes part in all of its pushes, since rows grow with the lane)
-struct WaveSink {
-  unsigned long long pending = 0;  // failures counted since the buffer filled up
-  bool full = false;
-};
-
-// called by all active lanes of the wave together; `fail` lanes record {kind, index, row}
-__device__ __forceinline__ void sink_push(const CheckSink& s, WaveSink& w, bool fail, uint32_t kind, uint32_t index,
-                                          uint32_t row) {
-  const unsigned long long m = __ballot(fail);
-  if (!m) return;
-  const unsigned long long cnt = (unsigned long long)__popcll(m);
-  if (w.full) {
-    w.pending += cnt;
-    return;
-  }
-  const int lane = threadIdx.x & 63;
-  const int leader = __ffsll(m) - 1;
-  unsigned long long base = 0;
-  if (lane == leader) base = atomicAdd(s.total, cnt);
-  base = __shfl(base, leader);
-  if (fail) {
-    const unsigned long long at = base + (unsigned long long)__popcll(m & ((1ull << lane) - 1));
-    if (at < s.cap) s.rec[at] = make_uint4(kind, index, row, 0u);
-  }
-  if (base + cnt >= s.cap) w.full = true;
-}
-
-// once per wave, after its last push, by all lanes that reach the end of the kernel
-__device__ __forceinline__ void sink_flush(const CheckSink& s, const WaveSink& w) {
-  if ((threadIdx.x & 63) == 0 && w.pending) atomicAdd(s.total, w.pending);
 }
 
 // ------------------------------------------------------------------ gates

@@ -1,5 +1,6 @@
 // proof_run.h -- one create_proof in flight (internal: prover.cpp, which defines the stages,
-// and prover_lookup.cpp, the lookup argument's permutation): the proof's inputs, the column
+// prover_lookup.cpp, the lookup argument's permutation, and prover_selfcheck.cpp, the
+// self-checks): the proof's inputs, the column
 // sets its stages transform, ProofRun and LookupPermute.
 #pragma once
 #include "assigned.h"
@@ -10,6 +11,7 @@ namespace prv {
 
 extern std::vector<std::pair<const char*, double>> g_stages;  // prover.cpp (h2g_prover_stages)
 extern bool g_stage_sync;  // h2g_prover_stage_sync: stage times = GPU completion times
+void self_check_reset();   // prover_selfcheck.cpp: h2g_last_self_check reports nothing
 
 // Debug aid: a build with -DH2G_DUMP_DIR='"<dir>"' writes named intermediates (raw Fr
 // arrays) of create_proof to <dir>/p<pid>/<name>.bin, one directory per process (rank); no
@@ -458,6 +460,19 @@ struct ProofRun {
     for (int c = 0; c < ncirc; c++) W[c] = pk.cws[c].get();
     std::memset(challenges.data(), 0, challenges.size() * sizeof(Fr));
   }
+  // the self-checks (prover_selfcheck.cpp; pk.self_check, fixed for the run): mode 2's checks
+  // queue behind the kernels that made what they read, into circuit ci's record sink; the
+  // verdict (and, when it fails, the location) follows openings_and_evals
+  const int sc_mode = pk.self_check;
+  static constexpr size_t SC_REC_CAP = 4096;  // records kept per circuit; the totals stay exact
+  CheckSink sc_sink(int ci) const;
+  int self_check_begin();
+  int sc_unusable_rows(int ci, const std::vector<int>& cols);
+  int sc_lookup_permuted();
+  int sc_permutation(int i);
+  int sc_product(int ci, uint32_t index, const Fr* z, const Fr* num_a, const Fr* num_b, const Fr* den_a,
+                 const Fr* den_b);
+  int self_check();
   int instances();
   int advice_phases();
   int lookup_permuted();

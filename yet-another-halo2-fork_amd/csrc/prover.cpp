@@ -249,6 +249,7 @@ int ProofRun::advice_phases() {
         }
         if (early || ncc == COPY_COLS_MAX || !from_dev) RCCHK(flush());
         if (early) {
+          if (sc_mode) RCCHK(sc_unusable_rows(ci, {c}));
           if (!pk.unblinded[c]) {
             Fr* rows = blind_rows + (size_t)c * (bf + 1);
             draw_rows(rows, bf + 1);
@@ -258,6 +259,7 @@ int ProofRun::advice_phases() {
         }
       }
       RCCHK(flush());
+      if (!early && sc_mode) RCCHK(sc_unusable_rows(ci, cols));
       if (!early) {  // every column's rows drawn in order, then one upload for the phase
         HIPCHK(pk.blind_d.ensure((size_t)pk.cs.A * (bf + 1)));
         std::vector<CopySeg> segs;
@@ -340,6 +342,7 @@ int ProofRun::lookup_permuted() {
     for (const Fr& f : all) lk_ok = lk_ok && f.is_zero();
   }
   if (!lk_ok) return fail(H2G_ERR_ARG, "create_proof: lookup input value not in the table (ConstraintSystemFailure)");
+  RCCHK(sc_lookup_permuted());
   Cols perm;  // (A'_l, S'_l) in transcript order
   for (CircuitWs* w : W) perm.lookup_permuted(*w);
   std::vector<int> own2(2 * NLT);
@@ -472,6 +475,7 @@ int ProofRun::permutation_products() {
         HIPCHK(perm_z_assemble(w.z_lag[s], n, bf, pk.pre, pk.last_z, pk.small, st));
         HIPCHK(hipMemcpyAsync(pk.last_z, w.z_lag[s] + (n - (size_t)(bf + 1)), sizeof(Fr), hipMemcpyDeviceToDevice,
                               st));
+        RCCHK(sc_permutation(i));
         if (ci == 0 && s == 0) {
           dump("z0", w.z_lag[s], n, st);
           dump("sigma0", pk.sigma_lag[0], n, st);
@@ -547,15 +551,18 @@ int ProofRun::lookup_shuffle_products() {
     for (int l = 0; l < pk.cs.NL; l++, j++) {
       CircuitWs* w = W[ci];
       RCCHK(finish_z(w->lk_z_poly[l], w->lk_z[l], w->lk_z_poly[l], w->lk_zc[l], true, mine(j), !lz_wide));
+      RCCHK(sc_product(ci, (uint32_t)l, w->lk_z[l], w->lk_a[l], w->lk_s[l], w->lk_ap[l], w->lk_sp[l]));
     }
-  for (CircuitWs* w : W)
+  for (int ci = 0; ci < ncirc; ci++)
     for (int s = 0; s < pk.cs.NS; s++) {
+      CircuitWs* w = W[ci];
       RCCHK(compress(*w, pk.seg_sh_in[s], pk.tmp_a));
       RCCHK(compress(*w, pk.seg_sh_sh[s], pk.tmp_b));
       HIPCHK(shuffle_prod_den(pk.tmp_b, gamma, pk.mod, n, st));
       HIPCHK(poly_batch_invert(pk.mod, n, pk.scr, st));
       HIPCHK(shuffle_prod_num(pk.tmp_a, gamma, pk.mod, n, st));
       RCCHK(finish_z(pk.mod, w->sh_z[s], w->sh_z_poly[s], w->sh_zc[s], false, true, true));
+      RCCHK(sc_product(ci, (uint32_t)(pk.cs.NL + s), w->sh_z[s], pk.tmp_a, nullptr, pk.tmp_b, nullptr));
     }
   RCCHK(xform(zc, nullptr));
   // product commitments: every circuit's lookups, then every circuit's shuffles
@@ -922,6 +929,9 @@ namespace {
 // priorities (transforms low, or MSMs high) measured slower (profiles/r06/xs/).
 int prove_impl(Device* d, Params& prm, ProvingKey& pk, const ProveIn& in, std::vector<uint8_t>* proof) {
   hipStream_t st = d->stream;
+  if (pk.self_check && (g_spmd.world > 1 || g_shard.world > 1))
+    return fail(H2G_ERR_STATE, "create_proof: the self-check (h2g_pk_set_self_check) does not run under a shard or "
+                               "SPMD transport");
   if (pk.cosets && g_spmd.world > 1)
     return fail(H2G_ERR_STATE, "create_proof: a streamed-coset key does not prove under an SPMD transport of " +
                                    std::to_string(g_spmd.world) + " ranks (make the key with H2G_COSETS_RESIDENT)");
@@ -942,6 +952,7 @@ int prove_impl(Device* d, Params& prm, ProvingKey& pk, const ProveIn& in, std::v
     HIPCHK(hipEventCreateWithFlags(&d->xev_done, hipEventDisableTiming));
   }
   ProofRun run(d, prm, pk, in, proof, E_sub, pieces, xsplit);
+  RCCHK(run.self_check_begin());
   RCCHK(run.instances());
   RCCHK(run.advice_phases());
   RCCHK(run.lookup_permuted());
@@ -951,6 +962,7 @@ int prove_impl(Device* d, Params& prm, ProvingKey& pk, const ProveIn& in, std::v
   RCCHK(run.eval_h());
   RCCHK(run.h_commit());
   RCCHK(run.openings_and_evals());
+  RCCHK(run.self_check());
   return pk.multiopen == 1 ? run.gwc() : run.shplonk();
 }
 
@@ -975,6 +987,7 @@ int create_proof_entry(Device* d, uint64_t params, uint64_t pk, ProveIn& in, uin
   int rc = prove_impl(d, *ip, K, in, &out);
   if (rc) {
     (void)hipStreamSynchronize(d->stream);
+    if (rc == H2G_ERR_UNSATISFIED) *proof_len = 0;  // refused by the self-check: no proof
     return rc;
   }
   *proof_len = out.size();
@@ -1008,6 +1021,7 @@ int h2g_create_proof(uint64_t params, uint64_t pk, const uint64_t* advice, int a
                      const uint64_t* instance, const uint32_t* instance_lens, const uint8_t rng_seed[32],
                      uint32_t vanishing_threads, uint8_t* proof, size_t proof_cap, size_t* proof_len) {
   NEED_DEV_P();
+  self_check_reset();  // h2g_last_self_check speaks of this call from here on
   if (!rng_seed) return fail(H2G_ERR_ARG, "create_proof: null rng seed");
   ProverRng rng(rng_seed);
   ProveIn in;
@@ -1024,6 +1038,7 @@ int h2g_create_proof_phased(uint64_t params, uint64_t pk, const h2g_witness_sour
                             const uint64_t* instance, const uint32_t* instance_lens, const uint8_t rng_seed[32],
                             uint32_t vanishing_threads, uint8_t* proof, size_t proof_cap, size_t* proof_len) {
   NEED_DEV_P();
+  self_check_reset();  // h2g_last_self_check speaks of this call from here on
   if (!rng_seed || !witness || !witness->fill) return fail(H2G_ERR_ARG, "create_proof: null argument");
   ProverRng rng(rng_seed);
   ProveIn in;
@@ -1038,6 +1053,7 @@ int h2g_create_proof_phased(uint64_t params, uint64_t pk, const h2g_witness_sour
 int h2g_create_proof_multi(uint64_t params, uint64_t pk, const h2g_prove_inputs* p, uint8_t* proof,
                            size_t proof_cap, size_t* proof_len) {
   NEED_DEV_P();
+  self_check_reset();  // h2g_last_self_check speaks of this call from here on
   if (!p || p->num_circuits < 1) return fail(H2G_ERR_ARG, "create_proof: no circuits");
   if (p->witness && !p->witness->fill) return fail(H2G_ERR_ARG, "create_proof: null witness fill");
   std::unique_ptr<ProverRng> rng;
@@ -1052,6 +1068,7 @@ int h2g_create_proof_multi(uint64_t params, uint64_t pk, const h2g_prove_inputs*
 int h2g_create_proof_assigned(uint64_t params, uint64_t pk, const h2g_prove_inputs* p,
                               const h2g_assigned_source* source, uint8_t* proof, size_t proof_cap, size_t* proof_len) {
   NEED_DEV_P();
+  self_check_reset();  // h2g_last_self_check speaks of this call from here on
   if (!p || p->num_circuits < 1) return fail(H2G_ERR_ARG, "create_proof: no circuits");
   if (!source || !source->fill) return fail(H2G_ERR_ARG, "create_proof_assigned: null source");
   if (p->advice || p->witness)

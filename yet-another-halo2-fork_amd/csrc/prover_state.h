@@ -1,7 +1,8 @@
 // prover_state.h -- what the prover's translation units share (internal: included only by
 // params.cpp, commit.cpp, keygen.cpp, spmd.cpp, pk_serde.cpp, check_witness.cpp, verifier.cpp,
-// g1_fft.hip, through multiopen.h by multiopen.cpp and kzg.cpp, and through proof_run.h by
-// prover.cpp and prover_lookup.cpp):
+// g1_fft.hip, through multiopen.h by multiopen.cpp and kzg.cpp, through vanishing.h by the
+// verifier and the self-check, and through proof_run.h by prover.cpp, prover_lookup.cpp and
+// prover_selfcheck.cpp):
 // the params / proving-key / workspace objects, the library's globals and the prototypes of
 // the functions that cross files.  Each global is defined in the file that owns it.
 #pragma once
@@ -178,6 +179,7 @@ struct ProvingKey {
   // 0 ProverSHPLONK, 1 ProverGWC; GWC witness polynomials, one per opening point
   int multiopen = 0;
   int transcript = 0;  // TRANSCRIPT_BLAKE2B / TRANSCRIPT_KECCAK256 (transcript.h)
+  int self_check = 0;  // h2g_pk_set_self_check (H2G_SELFCHECK_*)
   std::vector<Fr*> gwc_q;
   static constexpr int LKC = 8;
   // the lookups' gathers and matches on LKS streams (lookup j's on stream j mod LKS), each
@@ -317,6 +319,10 @@ struct ProvingKey {
   // thread count: the next proof generates and commits the random polynomial early
   int64_t van_pos = -1;
   uint32_t van_T = 0;
+  // the self-checks' record slots and counters, one set per circuit of a proof (grow-only,
+  // allocated by the first checked proof)
+  DevArr<uint4> sc_rec;
+  DevArr<unsigned long long> sc_total;
   // h2g_check_witness's own buffers (grow-only, allocated by the first check): the record
   // buffer and counters, the blinding rows' generator inputs and values, the full sort's
   // keys / indices / scratch and its two sorted outputs, the copy list and column table

@@ -28,6 +28,7 @@
 #include "multiopen.h"
 #include "pairing.h"
 #include "pairing_dev.h"
+#include "vanishing.h"
 
 using namespace h2g;
 using namespace h2g::rt;
@@ -168,23 +169,6 @@ struct ProofReader {
   }
 };
 
-Fr rotate_omega(const Shape& sh, const Fr& x, int64_t rot) {
-  return x * pow_u64(rot >= 0 ? sh.omega : sh.omega_inv, (uint64_t)(rot >= 0 ? rot : -rot));
-}
-// l_i_range (domain.rs:425-450): L_rot(x) for rot in [lo, hi)
-std::vector<Fr> l_i_range(const Shape& sh, const Fr& x, const Fr& xn, int64_t lo, int64_t hi) {
-  const Fr common = (xn - Fr::one()) * sh.bary;
-  std::vector<Fr> out;
-  if (hi <= lo) return out;
-  out.reserve((size_t)(hi - lo));
-  Fr w = rotate_omega(sh, Fr::one(), lo);
-  for (int64_t rot = lo; rot < hi; rot++) {
-    out.push_back(inv(x - w) * common * w);
-    w = w * sh.omega;
-  }
-  return out;
-}
-
 // fills left / right with the DualMSM's terms; false: the proof is malformed
 bool proof_terms(const Shape& sh, const h2g_verify_item& it, const G1Affine* pts, uint32_t base0, Msm* left_out,
                  Msm* right_out) {
@@ -247,56 +231,32 @@ bool proof_terms(const Shape& sh, const h2g_verify_item& it, const G1Affine* pts
   const Fr x = T.squeeze();
   if (!R.ok) return false;
   const Fr xn = pow_u64(x, n);
-  // instance evaluations (QUERY_INSTANCE = false): inner products with l_i_range
-  std::vector<std::vector<Fr>> ins_ev(NC, std::vector<Fr>(cs.ins_q.size(), Fr::zero()));
-  if (!cs.ins_q.empty()) {
-    int min_rot = 0, max_rot = 0;
-    for (const auto& q : cs.ins_q) {
-      min_rot = std::min(min_rot, q.rot);
-      max_rot = std::max(max_rot, q.rot);
-    }
-    size_t max_len = 0;
-    for (const auto& ci : inst)
-      for (const auto& col : ci) max_len = std::max(max_len, col.size());
-    const std::vector<Fr> l_is = l_i_range(sh, x, xn, -(int64_t)max_rot, (int64_t)max_len + (int64_t)(-min_rot));
-    for (int c = 0; c < NC; c++)
-      for (size_t qi = 0; qi < cs.ins_q.size(); qi++) {
-        const auto& q = cs.ins_q[qi];
-        const size_t off = (size_t)(max_rot - q.rot);
-        const std::vector<Fr>& vals = inst[c][q.index];
-        Fr acc = Fr::zero();
-        for (size_t j = 0; j < vals.size() && off + j < l_is.size(); j++) acc = acc + vals[j] * l_is[off + j];
-        ins_ev[c][qi] = acc;
-      }
-  }
-  std::vector<std::vector<Fr>> adv_ev(NC, std::vector<Fr>(cs.adv_q.size()));
+  // the proof's values at x (vanishing.h): instance evaluations (QUERY_INSTANCE = false), then
+  // the evaluations the proof carries
+  const EvalDomain dom{n, sh.omega, sh.omega_inv, sh.bary};
+  VanishingEvals E;
+  E.chal = chal;
+  E.theta = theta, E.beta = beta, E.gamma = gamma, E.y = y, E.x = x;
+  E.ins_ev = instance_evals(cs, dom, x, xn, inst);
+  E.adv_ev.assign(NC, std::vector<Fr>(cs.adv_q.size()));
   for (int c = 0; c < NC; c++)
-    for (auto& e : adv_ev[c]) e = R.read_scalar();
-  std::vector<Fr> fix_ev(cs.fix_q.size());
-  for (auto& e : fix_ev) e = R.read_scalar();
+    for (auto& e : E.adv_ev[c]) e = R.read_scalar();
+  E.fix_ev.resize(cs.fix_q.size());
+  for (auto& e : E.fix_ev) e = R.read_scalar();
   const Fr random_ev = R.read_scalar();
-  std::vector<Fr> perm_ev(cs.P);
-  for (auto& e : perm_ev) e = R.read_scalar();
-  struct SetEv {
-    Fr e0, e1, e2;
-  };
-  std::vector<std::vector<SetEv>> sets(NC, std::vector<SetEv>(nsets));
+  E.perm_ev.resize(cs.P);
+  for (auto& e : E.perm_ev) e = R.read_scalar();
+  E.sets.assign(NC, std::vector<VanishingEvals::SetEv>(nsets));
   for (int c = 0; c < NC; c++)
     for (int i = 0; i < nsets; i++) {
-      sets[c][i].e0 = R.read_scalar();
-      sets[c][i].e1 = R.read_scalar();
-      sets[c][i].e2 = i + 1 < nsets ? R.read_scalar() : Fr::zero();
+      E.sets[c][i].e0 = R.read_scalar();
+      E.sets[c][i].e1 = R.read_scalar();
+      E.sets[c][i].e2 = i + 1 < nsets ? R.read_scalar() : Fr::zero();
     }
-  struct LkEv {
-    Fr z, zn, ap, api, sp;
-  };
-  struct ShEv {
-    Fr z, zn;
-  };
-  std::vector<std::vector<LkEv>> lk_ev(NC, std::vector<LkEv>(NL));
-  std::vector<std::vector<ShEv>> sh_ev(NC, std::vector<ShEv>(NS));
+  E.lk_ev.assign(NC, std::vector<VanishingEvals::LkEv>(NL));
+  E.sh_ev.assign(NC, std::vector<VanishingEvals::ShEv>(NS));
   for (int c = 0; c < NC; c++)
-    for (auto& e : lk_ev[c]) {
+    for (auto& e : E.lk_ev[c]) {
       e.z = R.read_scalar();
       e.zn = R.read_scalar();
       e.ap = R.read_scalar();
@@ -304,7 +264,7 @@ bool proof_terms(const Shape& sh, const h2g_verify_item& it, const G1Affine* pts
       e.sp = R.read_scalar();
     }
   for (int c = 0; c < NC; c++)
-    for (auto& e : sh_ev[c]) {
+    for (auto& e : E.sh_ev[c]) {
       e.z = R.read_scalar();
       e.zn = R.read_scalar();
     }
@@ -312,89 +272,7 @@ bool proof_terms(const Shape& sh, const h2g_verify_item& it, const G1Affine* pts
 
   // the vanishing argument: every circuit's expressions at x, one Horner chain in y
   const Fr one = Fr::one();
-  const std::vector<Fr> l_evals = l_i_range(sh, x, xn, -(int64_t)(cs.bf + 1), 1);
-  const Fr l_last = l_evals[0];
-  Fr l_blind = Fr::zero();
-  for (int i = 1; i < 1 + cs.bf; i++) l_blind = l_blind + l_evals[i];
-  const Fr l_0 = l_evals[1 + cs.bf];
-  const Fr active = one - (l_last + l_blind);
-  auto qindex = [](const std::vector<prv::Query>& qs, int type, int index, int rot) -> int {
-    for (size_t i = 0; i < qs.size(); i++)
-      if (qs[i].type == type && qs[i].index == index && qs[i].rot == rot) return (int)i;
-    return -1;
-  };
-  Fr h_eval = Fr::zero();
-  auto push = [&](const Fr& v) { h_eval = h_eval * y + v; };
-  const size_t num_nodes = cs.nodes.size() / 4;
-  std::vector<Fr> val(num_nodes);
-  const Fr delta = fr_delta();
-  for (int c = 0; c < NC; c++) {
-    auto qeval = [&](int t, int i, int r) -> Fr {
-      if (t == COL_ADVICE) {
-        const int q = qindex(cs.adv_q, t, i, r);
-        return q < 0 ? Fr::zero() : adv_ev[c][q];
-      }
-      if (t == COL_FIXED) {
-        const int q = qindex(cs.fix_q, t, i, r);
-        return q < 0 ? Fr::zero() : fix_ev[q];
-      }
-      const int q = qindex(cs.ins_q, t, i, r);
-      return q < 0 ? Fr::zero() : ins_ev[c][q];
-    };
-    for (size_t i = 0; i < num_nodes; i++) {  // children precede parents (check_nodes)
-      const int32_t* nd = &cs.nodes[4 * i];
-      switch (nd[0]) {
-        case OP_CONST: val[i] = cs.constants[nd[1]]; break;
-        case OP_QUERY: val[i] = qeval(nd[1], nd[2], nd[3]); break;
-        case OP_NEG: val[i] = Fr::zero() - val[nd[1]]; break;
-        case OP_SUM: val[i] = val[nd[1]] + val[nd[2]]; break;
-        case OP_PROD: val[i] = val[nd[1]] * val[nd[2]]; break;
-        default: val[i] = chal[nd[1]]; break;  // OP_CHALLENGE
-      }
-    }
-    for (int32_t g : cs.gate_roots) push(val[g]);
-    const std::vector<SetEv>& st = sets[c];
-    if (nsets) {  // permutation/verifier.rs:120-210
-      push(l_0 * (one - st[0].e0));
-      push((st[nsets - 1].e0 * st[nsets - 1].e0 - st[nsets - 1].e0) * l_last);
-      for (int i = 1; i < nsets; i++) push((st[i].e0 - st[i - 1].e2) * l_0);
-      for (int ci = 0; ci < nsets; ci++) {
-        const int lo = ci * cs.chunk_len, hi = std::min(cs.P, lo + cs.chunk_len);
-        Fr left = st[ci].e1;
-        for (int j = lo; j < hi; j++)
-          left = left * (qeval(cs.perm_cols[j].first, cs.perm_cols[j].second, 0) + beta * perm_ev[j] + gamma);
-        Fr right = st[ci].e0;
-        Fr cur = beta * x * pow_u64(delta, (uint64_t)lo);
-        for (int j = lo; j < hi; j++) {
-          right = right * (qeval(cs.perm_cols[j].first, cs.perm_cols[j].second, 0) + cur + gamma);
-          cur = cur * delta;
-        }
-        push((left - right) * active);
-      }
-    }
-    auto compress = [&](const std::vector<int32_t>& roots) {
-      Fr acc = Fr::zero();
-      for (int32_t r : roots) acc = acc * theta + val[r];
-      return acc;
-    };
-    for (int l = 0; l < NL; l++) {  // lookup/verifier.rs:98-160
-      const LkEv& e = lk_ev[c][l];
-      push(l_0 * (one - e.z));
-      push(l_last * (e.z * e.z - e.z));
-      const Fr left = e.zn * (e.ap + beta) * (e.sp + gamma);
-      const Fr right = e.z * (compress(cs.lk_in[l]) + beta) * (compress(cs.lk_tab[l]) + gamma);
-      push((left - right) * active);
-      push(l_0 * (e.ap - e.sp));
-      push((e.ap - e.sp) * (e.ap - e.api) * active);
-    }
-    for (int l = 0; l < NS; l++) {  // shuffle/verifier.rs
-      const ShEv& e = sh_ev[c][l];
-      push(l_0 * (one - e.z));
-      push(l_last * (e.z * e.z - e.z));
-      push(active * (e.zn * (compress(cs.sh_sh[l]) + gamma) - e.z * (compress(cs.sh_in[l]) + gamma)));
-    }
-  }
-  const Fr expected_h = h_eval * inv(xn - one);
+  const Fr expected_h = vanishing_expected_h(cs, dom, E);
   Msm h_msm;  // sum_i xn^i h_i
   {
     Fr p = one;
@@ -409,14 +287,14 @@ bool proof_terms(const Shape& sh, const h2g_verify_item& it, const G1Affine* pts
   std::vector<VerifierQ> queries;  // key: the commitment's base index, or KEY_H; pt: index into Shape::rots
   for (int c = 0; c < NC; c++) {
     for (size_t qi = 0; qi < cs.adv_q.size(); qi++)
-      queries.push_back({adv_cm[c][cs.adv_q[qi].index], sh.rot_id(cs.adv_q[qi].rot), adv_ev[c][qi]});
+      queries.push_back({adv_cm[c][cs.adv_q[qi].index], sh.rot_id(cs.adv_q[qi].rot), E.adv_ev[c][qi]});
     for (int i = 0; i < nsets; i++) {
-      queries.push_back({perm_cm[c][i], r0, sets[c][i].e0});
-      queries.push_back({perm_cm[c][i], r_next, sets[c][i].e1});
+      queries.push_back({perm_cm[c][i], r0, E.sets[c][i].e0});
+      queries.push_back({perm_cm[c][i], r_next, E.sets[c][i].e1});
     }
-    for (int i = nsets - 2; i >= 0; i--) queries.push_back({perm_cm[c][i], r_last, sets[c][i].e2});
+    for (int i = nsets - 2; i >= 0; i--) queries.push_back({perm_cm[c][i], r_last, E.sets[c][i].e2});
     for (int l = 0; l < NL; l++) {
-      const LkEv& e = lk_ev[c][l];
+      const VanishingEvals::LkEv& e = E.lk_ev[c][l];
       queries.push_back({lk_z[c][l], r0, e.z});
       queries.push_back({lk_a[c][l], r0, e.ap});
       queries.push_back({lk_s[c][l], r0, e.sp});
@@ -424,13 +302,13 @@ bool proof_terms(const Shape& sh, const h2g_verify_item& it, const G1Affine* pts
       queries.push_back({lk_z[c][l], r_next, e.zn});
     }
     for (int l = 0; l < NS; l++) {
-      queries.push_back({sh_z[c][l], r0, sh_ev[c][l].z});
-      queries.push_back({sh_z[c][l], r_next, sh_ev[c][l].zn});
+      queries.push_back({sh_z[c][l], r0, E.sh_ev[c][l].z});
+      queries.push_back({sh_z[c][l], r_next, E.sh_ev[c][l].zn});
     }
   }
   for (size_t qi = 0; qi < cs.fix_q.size(); qi++)
-    queries.push_back({sh.base_fixed(cs.fix_q[qi].index), sh.rot_id(cs.fix_q[qi].rot), fix_ev[qi]});
-  for (int i = 0; i < cs.P; i++) queries.push_back({sh.base_perm(i), r0, perm_ev[i]});
+    queries.push_back({sh.base_fixed(cs.fix_q[qi].index), sh.rot_id(cs.fix_q[qi].rot), E.fix_ev[qi]});
+  for (int i = 0; i < cs.P; i++) queries.push_back({sh.base_perm(i), r0, E.perm_ev[i]});
   queries.push_back({KEY_H, r0, expected_h});
   queries.push_back({random_cm, r0, random_ev});
   for (const auto& q : queries)

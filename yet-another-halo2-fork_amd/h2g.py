@@ -196,6 +196,13 @@ _SIGS = {
     "h2g_debug_assigned_per": ([SZ, ctypes.POINTER(I32)], I32),
     "h2g_debug_assigned_to_fr_dev": ([VP, SZ, VP, VP, SZ, VP, I32, VP], I32),
     "h2g_create_proof_assigned": ([U64, U64, VP, VP, ctypes.c_char_p, SZ, ctypes.POINTER(SZ)], I32),
+    "h2g_pk_set_self_check": ([U64, I32], I32),
+    "h2g_last_self_check": ([VP, SZ, ctypes.POINTER(U64)], I32),
+    "h2g_debug_selfcheck_product_dev": ([VP, VP, VP, VP, VP, U64P, U64P, U64, U64, I32, VP, SZ,
+                                         ctypes.POINTER(U64)], I32),
+    "h2g_debug_selfcheck_permuted_dev": ([VP, VP, U64, I32, VP, SZ, ctypes.POINTER(U64)], I32),
+    "h2g_debug_selfcheck_permutation_dev": ([VP, U64P, ctypes.POINTER(VP), ctypes.POINTER(VP), U64P, I32, U64P, U64P,
+                                             U64P, U64, VP, SZ, ctypes.POINTER(U64)], I32),
 }
 
 TRANSCRIPTS = {"blake2b": 0, "keccak256": 1}  # Blake2bWrite / Keccak256Write (h2g_pk_set_transcript)
@@ -205,7 +212,20 @@ _lib = None
 
 
 class H2GError(RuntimeError):
-    pass
+    """a nonzero return of the library: .code, and -- from a create_proof* that the self-check
+    refused (ERR_UNSATISFIED, or ERR_STATE from its argument checks) -- .failures, the
+    (kind, index, row, circuit) records of last_self_check(), with .total their exact number"""
+
+    def __init__(self, msg, code=None, failures=(), total=0):
+        super().__init__(msg)
+        self.code = code
+        self.failures = list(failures)
+        self.total = total
+
+
+class UnsatisfiedError(H2GError):
+    """H2G_ERR_UNSATISFIED: the prover's self-check refused a witness that does not satisfy the
+    circuit (ProvingKey.set_self_check); no proof was written"""
 
 
 def header_symbols():
@@ -231,9 +251,24 @@ def lib():
     return _lib
 
 
+ERR_ARG, ERR_DEVICE, ERR_NOMEM, ERR_STATE, ERR_HANDLE, ERR_UNSATISFIED = 1, 2, 3, 4, 5, 6
+
+
 def check(rc):
     if rc != 0:
-        raise H2GError(f"h2g error {rc}: {lib().h2g_last_error().decode()}")
+        raise H2GError(f"h2g error {rc}: {lib().h2g_last_error().decode()}", code=rc)
+
+
+def check_proof(rc):
+    """check() for the create_proof* entries: the self-check's records travel with the error"""
+    if rc == 0:
+        return
+    msg = f"h2g error {rc}: {lib().h2g_last_error().decode()}"
+    try:
+        total, recs = last_self_check()
+    except (H2GError, AttributeError):  # (an older A/B build lacks the entry point)
+        total, recs = 0, []
+    raise (UnsatisfiedError if rc == ERR_UNSATISFIED else H2GError)(msg, code=rc, failures=recs, total=total)
 
 
 def p64(a):
@@ -861,7 +896,63 @@ class CheckInputs(ctypes.Structure):
 
 # h2g_check_failure.kind, and the row of a failure that has none
 CHECK_GATE, CHECK_GATE_BLINDING, CHECK_LOOKUP, CHECK_SHUFFLE, CHECK_COPY = 1, 2, 3, 4, 5
+CHECK_PERMUTATION, CHECK_PRODUCT, CHECK_PERMUTED_PAIR, CHECK_UNUSABLE_ROW, CHECK_IDENTITY = 6, 7, 8, 9, 10
 CHECK_NO_ROW = 0xFFFFFFFF
+SELF_CHECK_MODES = {"off": 0, "verdict": 1, "arguments": 2}  # H2G_SELFCHECK_*
+
+
+def _records(out, got, circuit=True):
+    if circuit:
+        return [(out[i].kind, out[i].index, out[i].row, out[i].reserved) for i in range(got)]
+    return [(out[i].kind, out[i].index, out[i].row) for i in range(got)]
+
+
+def last_self_check(cap=256):
+    """h2g_last_self_check: what the self-check of the last create_proof* found ->
+    (total, [(kind, index, row, circuit), ...]), min(total, cap) records sorted by (circuit,
+    kind, index, row); (0, []) after a proof that was returned"""
+    out = (CheckFailure * max(cap, 1))()
+    total = U64()
+    check(lib().h2g_last_self_check(ctypes.cast(out, VP) if cap else None, cap, ctypes.byref(total)))
+    return total.value, _records(out, min(total.value, cap))
+
+
+def debug_selfcheck_product_dev(d_z, d_num_a, d_num_b, d_den_a, d_den_b, beta, gamma, n, u, max_blocks=0, cap=64):
+    """h2g_debug_selfcheck_product_dev (test seam): the grand-product check on device arrays
+    (pointers; d_num_b = d_den_b = None: the one-factor form); beta, gamma: Montgomery uint64[4]
+    -> (total, [(kind, index, row), ...])"""
+    out = (CheckFailure * max(cap, 1))()
+    total = U64()
+    vp = lambda p: VP(p) if p else None
+    check(lib().h2g_debug_selfcheck_product_dev(vp(d_z), vp(d_num_a), vp(d_num_b), vp(d_den_a), vp(d_den_b),
+                                                p64(np.ascontiguousarray(beta, dtype=np.uint64)),
+                                                p64(np.ascontiguousarray(gamma, dtype=np.uint64)), n, u, max_blocks,
+                                                ctypes.cast(out, VP) if cap else None, cap, ctypes.byref(total)))
+    return total.value, _records(out, min(total.value, cap), circuit=False)
+
+
+def debug_selfcheck_permutation_dev(d_z, first, d_values, d_sigmas, delta_pows, beta, gamma, omega, u, cap=64):
+    """h2g_debug_selfcheck_permutation_dev (test seam): one column set's permutation product;
+    d_values / d_sigmas: device pointers, one per column; first, beta, gamma, omega: Montgomery
+    uint64[4] (first None: one); delta_pows: (m, 4) -> (total, [(kind, index, row), ...])"""
+    m = len(d_values)
+    out = (CheckFailure * max(cap, 1))()
+    total = U64()
+    keep = [None if a is None else np.ascontiguousarray(a, dtype=np.uint64)
+            for a in (first, delta_pows, beta, gamma, omega)]
+    check(lib().h2g_debug_selfcheck_permutation_dev(VP(d_z), p64(keep[0]), (VP * m)(*d_values), (VP * m)(*d_sigmas),
+                                                    p64(keep[1]), m, p64(keep[2]), p64(keep[3]), p64(keep[4]), u,
+                                                    ctypes.cast(out, VP) if cap else None, cap, ctypes.byref(total)))
+    return total.value, _records(out, min(total.value, cap), circuit=False)
+
+
+def debug_selfcheck_permuted_dev(d_a, d_s, u, max_blocks=0, cap=64):
+    """h2g_debug_selfcheck_permuted_dev (test seam) -> (total, [(kind, index, row), ...])"""
+    out = (CheckFailure * max(cap, 1))()
+    total = U64()
+    check(lib().h2g_debug_selfcheck_permuted_dev(VP(d_a), VP(d_s), u, max_blocks,
+                                                 ctypes.cast(out, VP) if cap else None, cap, ctypes.byref(total)))
+    return total.value, _records(out, min(total.value, cap), circuit=False)
 
 
 def _ptr(a, t):
@@ -1098,11 +1189,17 @@ class ProvingKey:
                     + 16 * (len(circ.lookups) + len(circ.shuffles)))
         buf = ctypes.create_string_buffer(cap)
         ln = SZ()
-        check(lib().h2g_create_proof(self.params.handle, self.handle, adv_p, on_dev, p64(ins),
-                                     lens.ctypes.data_as(ctypes.POINTER(U32)), bytes(seed), vanishing_threads,
-                                     buf, cap, ctypes.byref(ln)))
+        check_proof(lib().h2g_create_proof(self.params.handle, self.handle, adv_p, on_dev, p64(ins),
+                                           lens.ctypes.data_as(ctypes.POINTER(U32)), bytes(seed), vanishing_threads,
+                                           buf, cap, ctypes.byref(ln)))
         del adv
         return buf.raw[: ln.value]
+
+    def set_self_check(self, mode):
+        """h2g_pk_set_self_check: "off" (the default), "verdict" -- create_proof* refuses a
+        witness whose proof would not verify (UnsatisfiedError, its .failures saying where) --
+        or "arguments": also the reference's `sanity-checks` while each argument is built"""
+        check(lib().h2g_pk_set_self_check(self.handle, SELF_CHECK_MODES.get(mode, mode)))
 
     def check_witness(self, wit, challenges=None, seed=None, copies=True, cap=64, advice_dev_ptr=None):
         """h2g_check_witness: MockProver::verify of a complete witness on the device ->
@@ -1166,9 +1263,9 @@ class ProvingKey:
                     + 16 * (len(circ.lookups) + len(circ.shuffles)))
         buf = ctypes.create_string_buffer(cap)
         ln = SZ()
-        check(lib().h2g_create_proof_phased(self.params.handle, self.handle, ctypes.byref(src), p64(ins),
-                                            lens.ctypes.data_as(ctypes.POINTER(U32)), bytes(seed),
-                                            vanishing_threads, buf, cap, ctypes.byref(ln)))
+        check_proof(lib().h2g_create_proof_phased(self.params.handle, self.handle, ctypes.byref(src), p64(ins),
+                                                  lens.ctypes.data_as(ctypes.POINTER(U32)), bytes(seed),
+                                                  vanishing_threads, buf, cap, ctypes.byref(ln)))
         ch = np.zeros((max(circ.num_challenges, 1), 4), dtype=np.uint64)
         cnt = ctypes.c_int()
         check(lib().h2g_last_challenges(p64(ch), circ.num_challenges, ctypes.byref(cnt)))
@@ -1259,11 +1356,11 @@ class ProvingKey:
         ln = SZ()
         try:
             if asrc is not None:
-                check(lib().h2g_create_proof_assigned(self.params.handle, self.handle, ctypes.byref(inp),
-                                                      ctypes.byref(asrc), buf, cap, ctypes.byref(ln)))
+                check_proof(lib().h2g_create_proof_assigned(self.params.handle, self.handle, ctypes.byref(inp),
+                                                            ctypes.byref(asrc), buf, cap, ctypes.byref(ln)))
             else:
-                check(lib().h2g_create_proof_multi(self.params.handle, self.handle, ctypes.byref(inp), buf, cap,
-                                                   ctypes.byref(ln)))
+                check_proof(lib().h2g_create_proof_multi(self.params.handle, self.handle, ctypes.byref(inp), buf,
+                                                         cap, ctypes.byref(ln)))
         finally:
             if native_rng is not None:
                 lib().h2g_rng_free(native_rng.value)
